@@ -2,13 +2,16 @@
 """Headline benchmark: training images/sec of MobileNetV2-FPN RetinaNet, 512x512, batch 2 per GPU
 (BASELINE.json configs[1]), one process per GPU, gradients averaged with RCCL over xGMI.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1 without a launcher: starts its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                               (N > 1 without a launcher: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = anchor assignment for the batch + forward + focal/smooth-L1 loss + backward + gradient all-reduce (the
 heads + FPN slice under the backbone's backward pass) + momentum optimizer, fp32, dropout 0.2 (reference default), on a
 synthetic COCO-shaped batch [image, hflip(image)] that is resident in HBM before the timed region.
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times exactly K steps
+(`ms_per_step`) and prints the headline; --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+Everything else is measured only with --full (each leg can still be left out with its --no-* switch):
   roofline     : the dominant kernel INSIDE the step -- the forward products of a Winograd F(4x4,3x3) head-tower layer
                  (36 x [682x256] x [256x256], 17 launches per step; the two backward product launches of the same layer are
                  `entries[0]`) -- timed from a replayed hipGraph with HIP events on the launch stream.  The products run on
@@ -21,7 +24,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) including
   nms          : decode + candidate scan + hand-written segment sort + class-wise NMS at BASELINE configs[4]'s shape, fp16
                  logits / box deltas as the fp16 net writes them (sigmoid inside the scan), ~1 % hot and the stress input;
   cpu_baseline : the CPU oracle (restatement of the reference's TF semantics, TF itself is not installable) timed on
-                 this host's cores on bounded samples: the cfg-2 train step, the cfg-1 (shapes 256^2) step, decode + NMS.
+                 this host's cores on bounded samples: the cfg-2 train step, the cfg-1 (shapes 256^2) step, decode + NMS;
+  extras       : (one GPU) collective stand-in, RCCL world-1 collective path, fresh-data loop, cfg 1 / 3 / 4, cfg-5 inference;
+  with ranks   : the one-graph-per-part path with eager collectives (its exposed all-reduce time) and the per-slice RCCL bus rates.
 """
 import argparse
 import json
@@ -59,6 +64,8 @@ X3_FWD_GRID = lambda tiles: 36 * (-(-tiles // 128)) * 2       # noqa: E731
 PRODUCT_REPS = 8                    # back-to-back launches per graph when the product kernels are timed alone (_graph_time)
 FP16_MFMA_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md: dense fp16 / bf16 matrix peak
 INFERENCE_GFLOP_PER_IMAGE = 596.0   # cfg 5 forward, 297.98 GMAC per 1024^2 image
+DUMP_MAX_BYTES = 64 << 20           # --dump-outputs: all files together
+DUMP_GRAD_SAMPLE = 1 << 20          # gradient elements kept (fixed seeded positions): the weights take most of the budget
 
 
 def synthetic_objects(rng, image_size=IMAGE_SIZE, max_obj=MAX_OBJ):
@@ -129,6 +136,25 @@ class Step(object):
     def __call__(self):
         out = self.trainer.step()
         return out['class_loss'], out['regr_loss']
+
+
+def dump_outputs(step, out_dir):
+    """What the last timed step computed, as float32 .npy files under `out_dir` (two builds compared output for output):
+      class_loss, regr_loss, regularization_loss : what Trainer.step returns;
+      weights        : every trainable parameter after the update, in arena order, padding dropped;
+      grads_sample   : the gradient the update applied, at DUMP_GRAD_SAMPLE fixed positions (seeded, sorted) of the same order."""
+    tr = step.trainer
+    torch.cuda.synchronize()
+    keep = np.concatenate([np.arange(o, o + s) for o, s in tr.arena.offsets])
+    pick = np.sort(np.random.default_rng(0).choice(keep.size, min(DUMP_GRAD_SAMPLE, keep.size), replace=False))
+    arrays = {k: tr.last[k].detach().float().reshape(1).cpu().numpy() for k in ("class_loss", "regr_loss", "regularization_loss")}
+    arrays["weights"] = tr.arena.weights.cpu().numpy()[keep]
+    arrays["grads_sample"] = tr.arena.grads.cpu().numpy()[keep[pick]]
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "outputs of %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _graph_time(fn, iters=100, reps=1):
@@ -772,15 +798,22 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="launch kernels eagerly instead of replaying hipGraphs")
     ap.add_argument("--loss", default="focal", choices=["focal", "bce_dice"])
     ap.add_argument("--dropout", type=float, default=0.2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-nms", action="store_true", help="skip the decode+NMS throughput measurement")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the kernel micro-timings behind `roofline`")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-GPU extras (collective stand-in, fresh-data loop, cfg 1 / 3 / 4, cfg-5 inference)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure roofline, NMS, extras, the CPU baseline (each can be left out below) "
+                         "and, with several ranks, the eager-collective path and the per-slice all-reduce rates")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; same arguments -> same inputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-nms", action="store_true", help="with --full: skip the decode+NMS throughput measurement")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the kernel micro-timings behind `roofline`")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the single-GPU extras (collective stand-in, fresh-data loop, cfg 1 / 3 / 4, cfg-5 inference)")
     ap.add_argument("--no-overlap", action="store_true", help="one backward segment, all-reduce after it (A/B aid)")
     ap.add_argument("--spawn", action="store_true", help="go through the rank launcher even for --gpus 1")
     ap.add_argument("--force-collective", action="store_true",
                     help="issue the RCCL all-reduces even with one rank (self-test of the multi-GPU path on a 1-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if not launched and (args.gpus > 1 or args.spawn):
@@ -848,11 +881,14 @@ def main():
         step, elapsed, exposed, losses, timeouts = run_once()
         if timeouts:
             raise SystemExit("bench.py: GroupNorm exchange timeouts with the grid-resident path off: invalid run")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step, args.dump_outputs)       # before anything below steps this trainer again
 
     # multi-GPU evidence, collected on every rank (collectives) before rank 0 prints: per-rank exposed time, per-slice bus rate
+    # (--full: the second path's run and the per-slice timings)
     dist_info = None
     segmented = None
-    if dist is not None and step.trainer.allreduce.active and step.trainer._graphs and step.trainer._graphs[5]:
+    if args.full and dist is not None and step.trainer.allreduce.active and step.trainer._graphs and step.trainer._graphs[5]:
         # the collectives are nodes of the step's graph: no event can be put around the final wait.  The time the compute stream
         # waits for collectives after the last backward kernel is measured on the OTHER path -- one graph per part, eager
         # collectives between them (what runs where RCCL's all-reduce cannot be captured) -- in a short second run, every rank
@@ -868,8 +904,9 @@ def main():
         dist.all_gather(per_rank, torch.tensor([exposed_tr.allreduce_exposed_ms()], dtype=torch.float64, device=device))
         per_rank = [float(t.item()) for t in per_rank]
         dist_info = {"rccl_ranks": world, "allreduce_exposed_ms_per_rank": [round(x, 4) for x in per_rank],
-                     "allreduce_exposed_ms_max": round(max(per_rank), 4), "allreduce_exposed_ms_mean": round(sum(per_rank) / world, 4),
-                     "slices": allreduce_slices(step.trainer)}
+                     "allreduce_exposed_ms_max": round(max(per_rank), 4), "allreduce_exposed_ms_mean": round(sum(per_rank) / world, 4)}
+        if args.full:
+            dist_info["slices"] = allreduce_slices(step.trainer)
         if segmented is not None:
             dist_info["one_graph_per_part_eager_collectives"] = segmented
             exposed = segmented["allreduce_exposed_ms"]
@@ -942,12 +979,12 @@ def main():
         }
         if dist_info is not None:
             result["config"]["allreduce"].update(dist_info)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             main, second, gn = roofline_kernels(device)
             result["roofline"] = dict(main, entries=[second, gn])
-        if not args.no_nms:
+        if args.full and not args.no_nms:
             result["nms"] = nms_benchmark(device)
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             # single-GPU extras (all driver-timed inside this run): the stand-in for a collective under the backward pass, the
             # product's own loop on fresh data, cfg 1 / 3 / 4 per-GPU workloads, cfg 5 inference
             if not args.no_graph:
@@ -970,7 +1007,7 @@ def main():
             torch.cuda.empty_cache()
             result["inference"] = inference_benchmark(device)
             torch.cuda.empty_cache()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline()
     # RCCL prints a version banner through C stdio when a communicator is created; on a pipe that buffer would be flushed at
     # exit, AFTER the line below -- flush it now on every rank so that the JSON line is the last thing on stdout

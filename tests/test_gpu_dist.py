@@ -59,7 +59,7 @@ def test_rccl_world1_forced_collectives_bit_equal_to_plain_step(tmp_path):
 
 def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus N` without a launcher starts the ranks itself (here N = 1 through the same path)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--force-collective",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--force-collective", "--full",
                         "--steps", "4", "--warmup", "3", "--no-cpu-baseline", "--no-nms", "--no-roofline", "--no-extras"],
                        env={k: v for k, v in _env().items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")},
                        timeout=900, capture_output=True, text=True)

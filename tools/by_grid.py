@@ -16,7 +16,7 @@ def main(path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from src_hash import kernel_source_hash
     print("# kernel_source_sha: %s" % kernel_source_hash())
-    print("# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline ; "
+    print("# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ; "
           "dispatches grouped by (kernel, blocks)")
     print("%-62s %8s %7s %9s %9s %9s %10s" % ("kernel", "blocks", "calls", "avg_us", "min_us", "max_us", "total_ms"))
     for (name, blocks), d in sorted(agg.items(), key=lambda kv: -sum(kv[1])):
