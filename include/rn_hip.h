@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 407
+#define RN_API_VERSION 408
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -491,6 +491,20 @@ int rn_flip_width(const void* x, void* y, int64_t outer, int w, int64_t inner, i
  * NULL = no normalisation).  x [n,h,w,c] uint8 or fp32, y [n,oh,ow,c] fp32, c <= 8. */
 int rn_resize_bilinear_normalize(const void* x, int in_u8, float* y, int n, int h, int w, int c, int oh, int ow,
                                  const float* mean, const float* stdv, rn_stream_t stream);
+
+/* The same input pipeline for one raw uint8 image of ANY size, straight into the reference's batch of two (dataset.py:145-151,
+ * 182-204 rescale + [image, hflip]; augmentation.py:5-22 flip; train.py:48-49 preprocess_image): pair [2, oh, ow, 3] fp32,
+ * slot 0 = rn_resize_bilinear_normalize of the image (bit for bit), slot 1 = its h-flip.  The raw size and the resize ratios
+ * come from `desc`, a DEVICE struct uploaded with the sample; the caller computes hs = (h-1)/(oh-1) (0 when oh == 1) and
+ * ws = (w-1)/(ow-1) in fp32 as rn_resize_bilinear_normalize does, so no division happens on the device.  One capture of
+ * this call therefore serves every raw size that maps to (oh, ow).  Reads stay inside raw[0, raw_capacity) whatever `desc`
+ * holds.  mean / std: HOST arrays of 3 floats, both NULL = no normalisation. */
+typedef struct rn_resize_desc {
+  int32_t h, w;
+  float hs, ws;
+} rn_resize_desc;
+int rn_resize_pair_u8(const uint8_t* raw, int64_t raw_capacity, const rn_resize_desc* desc, float* pair, int oh, int ow,
+                      const float* mean, const float* stdv, rn_stream_t stream);
 
 /* ------------------------------------------------------------------ loss
  * Replaces utils.process_labels_and_logits/postprocess_and_mask (utils.py:240-284; the

@@ -63,3 +63,70 @@ extern "C" int rn_resize_bilinear_normalize(const void* x, int in_u8, float* y, 
   RN_LAUNCH_CHECK();
   return RN_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- ragged pair
+// One pass from a raw uint8 [h, w, 3] image of any size (read from a device descriptor at run time) to the reference's batch of
+// two [image, hflip(image)] (dataset.py:182-204, augmentation.py:5-22): the arithmetic of resize_bilinear_kernel, channel by
+// channel, one work item per output pixel, written to slot 0 at (oy, ox) and to slot 1 at (oy, ow-1-ox).  Since h, w, hs, ws
+// come from `desc`, one captured graph serves every raw size that maps to the same (oh, ow).  Every read is bounded by
+// raw_capacity: a bad descriptor gives wrong pixels, never an access outside the buffer.
+namespace {
+struct PairArgs {
+  const uint8_t* raw; int64_t cap;
+  const rn_resize_desc* desc;
+  float* y;
+  int oh, ow, normalize;
+  float mean[3], stdv[3];
+};
+
+__device__ __forceinline__ float fetch_u8(const uint8_t* raw, int64_t cap, int64_t idx) {
+  return (idx >= 0 && idx < cap) ? (float)raw[idx] * (1.0f / 255.0f) : 0.0f;  // convert_image_dtype
+}
+
+__global__ __launch_bounds__(256) void resize_pair_u8_kernel(const PairArgs a) {
+  const int h = a.desc->h, w = a.desc->w;
+  const float hs = a.desc->hs, ws = a.desc->ws;
+  const int64_t total = (int64_t)a.oh * a.ow;
+  const int64_t plane = total * 3;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int ox = (int)(i % a.ow), oy = (int)(i / a.ow);
+    const float iny = (float)oy * hs, inx = (float)ox * ws;
+    const float fy = floorf(iny), fx = floorf(inx);
+    // the clamps to [0, size-1] change nothing for a valid descriptor (the TF index arithmetic stays inside the image)
+    const int y0 = min(max((int)fy, 0), h - 1), x0 = min(max((int)fx, 0), w - 1);
+    const int y1 = max(min((int)ceilf(iny), h - 1), 0), x1 = max(min((int)ceilf(inx), w - 1), 0);
+    const float yl = iny - fy, xl = inx - fx;
+    const int64_t r0 = (int64_t)y0 * w, r1 = (int64_t)y1 * w;
+    const int64_t itl = (r0 + x0) * 3, itr = (r0 + x1) * 3, ibl = (r1 + x0) * 3, ibr = (r1 + x1) * 3;
+    float* o0 = a.y + i * 3;
+    float* o1 = a.y + plane + ((int64_t)oy * a.ow + (a.ow - 1 - ox)) * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float tl = fetch_u8(a.raw, a.cap, itl + ch), tr = fetch_u8(a.raw, a.cap, itr + ch);
+      const float bl = fetch_u8(a.raw, a.cap, ibl + ch), br = fetch_u8(a.raw, a.cap, ibr + ch);
+      const float top = tl + (tr - tl) * xl;
+      const float bot = bl + (br - bl) * xl;
+      float v = top + (bot - top) * yl;
+      if (a.normalize) v = (v - a.mean[ch]) / a.stdv[ch];
+      o0[ch] = v;
+      o1[ch] = v;
+    }
+  }
+}
+}  // namespace
+
+extern "C" int rn_resize_pair_u8(const uint8_t* raw, int64_t raw_capacity, const rn_resize_desc* desc, float* pair, int oh,
+                                 int ow, const float* mean, const float* stdv, rn_stream_t stream) {
+  RN_CHECK_ARG(raw && desc && pair && raw_capacity >= 3 && oh >= 1 && ow >= 1, "resize_pair_u8: bad argument");
+  RN_CHECK_ARG((mean == nullptr) == (stdv == nullptr), "resize_pair_u8: mean and std go together");
+  PairArgs a = {};
+  a.raw = raw; a.cap = raw_capacity; a.desc = desc; a.y = pair; a.oh = oh; a.ow = ow;
+  a.normalize = mean ? 1 : 0;
+  for (int i = 0; i < 3 && mean; ++i) { a.mean[i] = mean[i]; a.stdv[i] = stdv[i]; }
+  const int64_t total = (int64_t)oh * ow;
+  int64_t b = (total + 255) / 256;
+  if (b > 16384) b = 16384;
+  hipLaunchKernelGGL(resize_pair_u8_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, a);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
+}

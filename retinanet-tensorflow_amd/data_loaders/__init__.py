@@ -1,1 +1,1 @@
-"""Loader protocol of the reference (data_loaders/base.py:1-11) and the synthetic 'shapes' dataset."""
+"""Loader protocol of the reference (data_loaders/base.py:1-11), the synthetic 'shapes' dataset and the Pascal VOC / COCO readers."""

@@ -4,9 +4,10 @@
     cls, reg, masks = build_labels(image_size, class_ids, boxes, num_obj, levels, num_classes)
     # dicts P3..P7: [N,H,W,A,C] f32 one-hot (zero where IoU<0.5), [N,H,W,A,4] f32, [N,H,W,A] u8
 
-The tf.data input pipeline of the reference (file reading, JPEG decode, shuffle,
-dataset.py:145-233) is out of scope; what remains of it here is the
-label construction and the ``[image, hflip(image)]`` batch convention (dataset.py:182-204).
+The tf.data input pipeline of the reference (dataset.py:145-233) maps onto: the annotation readers
+(data_loaders/pascal.py, coco.py; epoch order in data_loaders/files.py), `decode_image` on the host (Pillow, an ordered
+pool of decode threads), and the device side below -- rescale, normalisation, the ``[image, hflip(image)]`` batch
+convention (dataset.py:182-204) and the label construction.
 """
 import ctypes as C
 import math
@@ -124,6 +125,30 @@ def rescale_image(image, scale=None, size=None, normalize=False, out=None):
     return y if batched else y[0]
 
 
+def resize_desc(hw, size):
+    """rn_resize_desc {h, w, hs, ws} of a raw (h, w) image resized to size = (oh, ow), as int32 [4] (the ratios' fp32 bits):
+    hs = (h-1)/(oh-1), 0 when oh == 1, in fp32 -- the values rn_resize_bilinear_normalize computes, bit for bit."""
+    h, w = int(hw[0]), int(hw[1])
+    oh, ow = int(size[0]), int(size[1])
+    ratios = np.array([np.float32(h - 1) / np.float32(oh - 1) if oh > 1 else 0.0,
+                       np.float32(w - 1) / np.float32(ow - 1) if ow > 1 else 0.0], np.float32)
+    return np.concatenate([np.array([h, w], np.int32), ratios.view(np.int32)])
+
+
+def resize_pair_u8(raw, desc, size, normalize=True, out=None):
+    """rn_resize_pair_u8: raw uint8 device buffer (any length; the image is its first h*w*3 bytes), desc int32 [4] device
+    tensor (resize_desc) -> [2, oh, ow, 3] fp32 = [rescale_image(image, normalize), its h-flip] in one launch."""
+    oh, ow = int(size[0]), int(size[1])
+    pair = torch.empty((2, oh, ow, 3), dtype=torch.float32, device=raw.device) if out is None else out
+    assert pair.is_contiguous() and tuple(pair.shape) == (2, oh, ow, 3) and pair.dtype == torch.float32
+    assert raw.dtype == torch.uint8 and desc.dtype == torch.int32 and desc.numel() == 4
+    mean = (C.c_float * 3)(*MEAN) if normalize else None
+    std = (C.c_float * 3)(*STD) if normalize else None
+    _rn.check(_rn.lib().rn_resize_pair_u8(_rn.ptr(raw), int(raw.numel()), _rn.ptr(desc), _rn.f32(pair), oh, ow, mean, std,
+                                          _rn.stream()), 'rn_resize_pair_u8')
+    return pair
+
+
 def preprocess_image(image):
     """(image - MEAN) / STD (train.py:48-49) for a float image already at its final size."""
     return rescale_image(image, size=tuple(image.shape[-3:-1]), normalize=True)
@@ -145,13 +170,71 @@ def sample_batch(image, boxes, class_ids, levels, num_classes, scale=None, num_o
     return {'image': pair, 'image_size': size, 'detection': {'classifications': c, 'regressions': r}, 'trainable_masks': m}
 
 
-def build_dataset(data_loader, levels, scale=None, shuffle=None, augment=False, device='cuda', normalize=True):
+def decode_image(path):
+    """tf.image.decode_jpeg(contents, channels=3) (dataset.py:158-160) on the host: uint8 [H, W, 3].  Pillow without draft()
+    (full-size decode), grey / CMYK / palette images through convert('RGB'), EXIF orientation ignored as TF ignores it, PNG
+    accepted as decode_jpeg accepts it."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise _rn.RnError("decoding image files needs Pillow (import PIL failed: %s)" % e)
+    if isinstance(path, bytes):
+        path = path.decode('utf-8')
+    with Image.open(path) as im:
+        if im.mode != 'RGB':
+            im = im.convert('RGB')
+        return np.asarray(im, dtype=np.uint8).copy()
+
+
+def decoded(samples, workers=4):
+    """The samples of `samples`, in order, each 'image_file' one decoded into 'image' by a pool of `workers` threads (at most
+    16; Pillow releases the GIL while it decodes).  Samples that already carry 'image' pass through untouched, and no pool
+    is started until the first 'image_file' sample.  When the decoded size differs from the annotated 'image_size', the
+    decoded size wins (the boxes are normalised by the image's own size downstream)."""
+    import collections
+    workers = max(1, min(16, int(workers)))
+
+    def load(s):
+        s = dict(s)
+        s['image'] = decode_image(s['image_file'])
+        s['image_size'] = tuple(s['image'].shape[:2])
+        return s
+
+    pool, pending = None, collections.deque()
+    try:
+        for s in samples:
+            if 'image' in s and not pending:
+                yield s
+                continue
+            if pool is None:
+                from concurrent.futures import ThreadPoolExecutor
+                pool = ThreadPoolExecutor(workers, thread_name_prefix='rn-decode')
+            pending.append(pool.submit(load, s) if 'image' not in s else _done(s))
+            if len(pending) >= 2 * workers:
+                yield pending.popleft().result()
+        while pending:
+            yield pending.popleft().result()
+    finally:
+        if pool is not None:
+            for f in pending:
+                f.cancel()
+            pool.shutdown(wait=True)
+
+
+def _done(value):
+    from concurrent.futures import Future
+    f = Future()
+    f.set_result(value)
+    return f
+
+
+def build_dataset(data_loader, levels, scale=None, shuffle=None, augment=False, device='cuda', normalize=True, decode_workers=4):
     """Generator form of dataset.py:154-215: per sample  decode -> boxes / image_size -> rescale_image ->
     build_labels -> [sample, hflip(sample)] batch -> preprocess_image.  Everything after the host loader runs on the
     device (sample_batch).  `shuffle` / `augment` are accepted for signature parity (the reference's augment_sample is a
     TODO stub; shuffling belongs to the loader here)."""
     dev = torch.device(device)
-    for sample in data_loader:
+    for sample in decoded(data_loader, decode_workers):
         image = torch.from_numpy(np.ascontiguousarray(sample['image'])).to(dev)                # uint8 or float [H,W,3]
         h, w = int(image.shape[0]), int(image.shape[1])
         boxes = np.asarray(sample['boxes'], np.float32) / np.asarray([h, w, h, w], np.float32)   # dataset.py:163
@@ -172,16 +255,34 @@ class DeviceFeed(object):
     sample once the previous segment A has consumed the buffers; the main stream waits for the upload), `features()` inside
     the segment, `consumed()` right after it.  The sample stream is the loader's, in order: a run through DeviceFeed sees
     exactly the samples `build_dataset` would yield.  A sample whose image size or object capacity differs from the
-    buffers' gets new buffers, and `shape_key` changes -- the trainer keeps one captured graph per key."""
+    buffers' gets new buffers, and `shape_key` changes -- the trainer keeps one captured graph per key.
 
-    def __init__(self, data_loader, levels, scale=None, device='cuda', max_obj=32, normalize=True, prefetch=3):
+    ragged=True (real images: many raw sizes, uint8 only): ONE pinned host slot set and ONE static device set hold the raw image
+    (a flat byte buffer), its rn_resize_desc, the boxes and the ids, sized once from the loader's `max_image_pixels()` /
+    `max_objects()` hints (objects rounded up to 32); without hints the capacity grows x1.5 when a sample needs more, and each
+    growth is a new generation.  `features()` is rn_resize_pair_u8 (raw size read from the descriptor at run time) + the
+    paired assignment, so the shape key is (oh, ow, object capacity, generation): one captured graph per NETWORK INPUT shape,
+    whatever raw sizes map to it.  'image_file' samples are decoded by `decode_workers` threads (`decoded`)."""
+
+    def __init__(self, data_loader, levels, scale=None, device='cuda', max_obj=32, normalize=True, prefetch=3, ragged=False,
+                 decode_workers=4):
         import queue
         import threading
         self.levels, self.scale, self.normalize = levels, scale, normalize
         self.num_classes = data_loader.num_classes
         self.device = torch.device(device)
         self.max_obj = int(max_obj)
-        self._it = iter(data_loader)
+        self.ragged = bool(ragged)
+        if self.ragged:
+            self._it = iter(decoded(data_loader, decode_workers))
+            px = getattr(data_loader, 'max_image_pixels', None)
+            ob = getattr(data_loader, 'max_objects', None)
+            self._raw_cap = 3 * int(px()) if callable(px) else 0          # bytes
+            self._obj_cap = max(self.max_obj, -(-int(ob()) // 32) * 32) if callable(ob) else self.max_obj
+            self._generation = 0 if self._raw_cap > 0 else -1            # -1: nothing allocated yet
+            self.generations = 0                                         # static device sets allocated so far
+        else:
+            self._it = iter(data_loader)
         self._slots = int(prefetch)
         self._free = queue.Queue()
         self._ready = queue.Queue()
@@ -207,6 +308,8 @@ class DeviceFeed(object):
 
     # -- host side: loader thread
     def _produce(self):
+        if self.ragged:
+            return self._produce_ragged()
         try:
             for sample in self._it:
                 slot = self._free.get()
@@ -237,6 +340,78 @@ class DeviceFeed(object):
             self._error = e
             self._ready.put(None)
 
+    def _produce_ragged(self):
+        try:
+            for sample in self._it:
+                slot = self._free.get()
+                if self._stop:
+                    return
+                if slot is not None and slot[1] is not None:
+                    slot[1].synchronize()
+                img = np.ascontiguousarray(sample['image'])
+                if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+                    raise ValueError("DeviceFeed(ragged=True) stages uint8 [H, W, 3] images, got %s %s" % (img.dtype, img.shape))
+                ids = np.asarray(sample['class_ids'], np.int32).reshape(-1)
+                h, w = int(img.shape[0]), int(img.shape[1])
+                boxes = (np.asarray(sample['boxes'], np.float32).reshape(-1, 4) / np.asarray([h, w, h, w], np.float32))   # dataset.py:163
+                if img.size > self._raw_cap or len(ids) > self._obj_cap:          # no hints, or a sample beyond them: grow
+                    self._raw_cap = max(img.size, -(-self._raw_cap * 3 // 2))
+                    self._obj_cap = max(self._obj_cap, -(-len(ids) // 32) * 32)
+                    self._generation += 1
+                oh, ow = rescale_size((h, w), self.scale) if self.scale is not None else (h, w)
+                host = slot[0] if slot is not None else None
+                if host is None or host['gen'] != self._generation:
+                    host = {'gen': self._generation,
+                            'raw': torch.empty((self._raw_cap,), dtype=torch.uint8).pin_memory(),
+                            'desc': torch.zeros((4,), dtype=torch.int32).pin_memory(),
+                            'boxes': torch.zeros((1, self._obj_cap, 4), dtype=torch.float32).pin_memory(),
+                            'ids': torch.zeros((1, self._obj_cap), dtype=torch.int32).pin_memory(),
+                            'nobj': torch.zeros((1,), dtype=torch.int32).pin_memory()}
+                host['raw'].numpy()[:img.size] = img.reshape(-1)
+                host['desc'].numpy()[:] = resize_desc((h, w), (oh, ow))
+                host['boxes'].zero_(); host['ids'].zero_()
+                host['boxes'].numpy()[0, :len(ids)] = boxes
+                host['ids'].numpy()[0, :len(ids)] = ids
+                host['nobj'][0] = len(ids)
+                host['bytes'], host['size'] = img.size, (oh, ow)
+                self._ready.put((host, {'boxes': boxes, 'class_ids': ids, 'image_hw': (h, w)}))
+            self._ready.put(None)
+        except BaseException as e:
+            self._error = e
+            self._ready.put(None)
+
+    def _stage_ragged(self, host, cur):
+        """stage() of the ragged mode: one static set per generation (the previous one is dropped with its generation)."""
+        key = (host['size'][0], host['size'][1], int(host['boxes'].shape[1]), host['gen'])
+        if self._static is None or self._static['gen'] != host['gen']:
+            self._static = {k: torch.empty(v.shape, dtype=v.dtype, device=self.device) for k, v in host.items()
+                            if isinstance(v, torch.Tensor)}
+            self._static['gen'] = host['gen']
+            self.generations += 1
+        self.shape_key = key
+        self._size = host['size']
+        cs = self._copy_stream
+        if self._consumed is not None:
+            cs.wait_event(self._consumed)
+        else:
+            cs.wait_stream(cur)
+        with torch.cuda.stream(cs):
+            n = host['bytes']
+            self._static['raw'][:n].copy_(host['raw'][:n], non_blocking=True)
+            for k in ('desc', 'boxes', 'ids', 'nobj'):
+                self._static[k].copy_(host[k], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(cs)
+        cur.wait_event(done)
+        return key, done
+
+    def _features_ragged(self):
+        s = self._static
+        oh, ow = self._size
+        pair = resize_pair_u8(s['raw'], s['desc'], (oh, ow), normalize=self.normalize)
+        c, r, m = build_labels((oh, ow), s['ids'], s['boxes'], self.levels, self.num_classes, num_obj=s['nobj'], flip_pair=True)
+        return {'image': pair, 'image_size': (oh, ow), 'detection': {'classifications': c, 'regressions': r}, 'trainable_masks': m}
+
     def close(self):
         self._stop = True
         for _ in range(self._slots + 1):
@@ -253,8 +428,14 @@ class DeviceFeed(object):
                 raise self._error
             raise StopIteration
         host, info = item
-        key = (tuple(host['image'].shape), str(host['image'].dtype), int(host['boxes'].shape[1]))
         cur = torch.cuda.current_stream(self.device)
+        if self.ragged:
+            key, done = self._stage_ragged(host, cur)
+            self._free.put((host, done))
+            self.last_sample = info
+            self.samples_staged += 1
+            return key
+        key = (tuple(host['image'].shape), str(host['image'].dtype), int(host['boxes'].shape[1]))
         if key != self.shape_key:
             if key not in self._statics:
                 self._statics[key] = {k: torch.empty(v.shape, dtype=v.dtype, device=self.device) for k, v in host.items()}
@@ -282,6 +463,8 @@ class DeviceFeed(object):
 
     def features(self):
         """The step's features from the static buffers (inside the captured segment when the trainer runs graphs)."""
+        if self.ragged:
+            return self._features_ragged()
         s = self._static
         return sample_batch(s['image'], s['boxes'], s['ids'], self.levels, self.num_classes, scale=self.scale,
                             num_obj=s['nobj'], normalize=self.normalize)

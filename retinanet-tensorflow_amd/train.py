@@ -19,6 +19,7 @@ import contextlib
 import ctypes
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -353,7 +354,8 @@ class Trainer(object):
         self._graphs = None
         # input shape key (dataset.DeviceFeed.shape_key; None without a feed) -> captured segments, least recently used first.
         # Every entry owns its graphs' private activation pool and static buffers, so the cache is BOUNDED (RN_GRAPH_CACHE, default 4
-        # shapes): a loader with many raw sizes should bucket / pad them; a key beyond the bound evicts the least recently used set
+        # shapes; a ragged DeviceFeed keys by network input shape, so raw image sizes do not count); a key beyond the bound evicts
+        # the least recently used set
         # (its next appearance re-captures: two warm-up passes + capture, logged).
         self._graph_cache = collections.OrderedDict()
         self.graph_cache_max = max(1, int(os.environ.get("RN_GRAPH_CACHE", "4")))
@@ -871,9 +873,9 @@ def _copy_tree(dst, src):
 
 
 # ------------------------------------------------------------------------------------------------ CLI
-# Minimal driver with the reference's flags (train.py:88-108).  Dataset readers (COCO / Pascal, cv2,
-# pycocotools) are out of scope; 'shapes' is a synthetic stand-in following data_loaders/shapes.py:133-176
-# (1-4 filled squares, half-size in [20, S/4], 3 classes), rendered with numpy.
+# Minimal driver with the reference's flags (train.py:88-108).  --dataset pascal ROOT SUBSET / coco ANN IMAGES read the
+# annotation files (data_loaders/pascal.py, coco.py; JPEG decode with Pillow on the host); 'shapes' is a synthetic stand-in
+# following data_loaders/shapes.py:133-176 (1-4 filled squares, half-size in [20, S/4], 3 classes), rendered with numpy.
 def evaluate(net, data_loader, levels, num_images, scale=None, device='cuda', score_threshold=0.5):
     """Inference + decode + class-wise NMS (train.py:68-85) over `num_images` samples of the loader, scored with
     COCO-style mAP and the reference's two IoU metrics (train.py:137-161); see metrics.py."""
@@ -915,7 +917,8 @@ def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--learning-rate', type=float, default=1e-2)
     parser.add_argument('--dropout', type=float, default=0.2)
-    parser.add_argument('--dataset', type=str, nargs='+', default=['shapes'])
+    parser.add_argument('--dataset', type=str, nargs='+', default=['shapes'],
+                        help='shapes [PATH NUM SIZE] | pascal ROOT SUBSET | coco ANN_JSON IMAGES_DIR')
     parser.add_argument('--epochs', type=int, default=1)
     parser.add_argument('--scale', type=int, default=256)
     parser.add_argument('--experiment', type=str, default=None, help='directory for checkpoints (model.safetensors)')
@@ -924,8 +927,14 @@ def build_parser():
                         default='mobilenet_v2')
     parser.add_argument('--optimizer', type=str, choices=['momentum', 'adam', 'rmsprop'], default='momentum')
     parser.add_argument('--loss', type=str, choices=['bce_dice', 'focal'], default='bce_dice')
-    parser.add_argument('--steps-per-epoch', type=int, default=100)
+    parser.add_argument('--steps-per-epoch', type=int, default=None,
+                        help='default: 100 for shapes, NUM for shapes PATH NUM SIZE, one pass of the shard for a file dataset')
+    parser.add_argument('--shape-runs', type=int, default=None,
+                        help='file datasets: runs of <= K samples of one network input size (default 8; 0 = plain shuffle)')
+    parser.add_argument('--decode-workers', type=int, default=4, help='threads decoding the image files (at most 16)')
     parser.add_argument('--eval-images', type=int, default=0, help='after training: mAP / IoU metrics over this many samples')
+    parser.add_argument('--eval-dataset', type=str, nargs='+', default=None,
+                        help='TYPE ARGS... as --dataset; required with --eval-images for a file dataset')
     parser.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of replaying the captured step')
     return parser
 
@@ -964,24 +973,51 @@ def broadcast_initial_state(trainer, src=0):
             dist.broadcast(trainer.opt.state2, src=src)
 
 
+LAST_RUN = {}
+
+
 def main(argv=None):
     import checkpoint
     import dataset
     import retinanet
-    args = build_parser().parse_args(argv)
-    assert args.dataset[0] == 'shapes', 'only the synthetic shapes loader is built in (file readers are out of scope)'
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    kind, dargs = args.dataset[0], args.dataset[1:]
+    files = kind in ('pascal', 'coco')
+    if kind not in ('shapes', 'pascal', 'coco') or len(dargs) != {'shapes': 3 if dargs else 0}.get(kind, 2):
+        parser.error('--dataset: shapes [PATH NUM SIZE] | pascal ROOT SUBSET | coco ANN_JSON IMAGES_DIR (got %s)' % ' '.join(args.dataset))
+    if files and args.eval_images and not args.eval_dataset:
+        parser.error('--eval-images with a file dataset needs --eval-dataset TYPE ARGS...')
     dev, rank, world, started = init_distributed()
     from data_loaders.shapes import Shapes
     # every replica draws its own samples (dataset.py:182-204: a replica's batch is [sample, hflip(sample)])
-    loader = Shapes(None, image_size=(args.scale + args.scale // 4, args.scale), seed=rank)   # rescale_image brings it to --scale
+    if files:
+        from data_loaders.inferred import Inferred
+        # one epoch = a permutation seeded by (0, epoch), sample i to rank i % world, runs of one network input size
+        loader = Inferred(kind, dargs).configure(seed=0, rank=rank, world=world, scale=args.scale, repeat=True,
+                                                 shape_runs=8 if args.shape_runs is None else args.shape_runs)
+        steps_per_epoch = args.steps_per_epoch or max(1, len(loader.records) // world)    # every rank runs the same steps
+        if rank == 0:
+            print('%s: %d images (%d skipped: no valid box), %d steps per epoch' % (kind, len(loader.records), loader.skipped,
+                                                                                  steps_per_epoch), flush=True)
+    elif dargs:
+        loader = Shapes(dargs[0], image_size=(int(dargs[2]), int(dargs[2])), seed=rank)
+        steps_per_epoch = args.steps_per_epoch or int(dargs[1])
+    else:
+        loader = Shapes(None, image_size=(args.scale + args.scale // 4, args.scale), seed=rank)   # rescale_image brings it to --scale
+        steps_per_epoch = args.steps_per_epoch or 100
     levels = build_levels()
     torch.manual_seed(0)                                                           # same initial weights on every rank
     net = retinanet.RetinaNet(backbone=args.backbone, levels=levels, num_classes=loader.num_classes, activation=L.elu,
                               dropout_rate=args.dropout).to(dev)
     # train_input_fn (train.py:190-202) = dataset.DeviceFeed: loader thread -> pinned host memory -> asynchronous upload ->
     # static device buffers; rescale, normalisation, the h-flip and the anchor assignment of every NEW sample run inside the
-    # captured step (one hipGraph per backward segment, replayed per step; --no-graph launches the same kernels eagerly)
-    feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev)
+    # captured step (one hipGraph per backward segment, replayed per step; --no-graph launches the same kernels eagerly).
+    # File datasets: ragged staging, one graph set per network input shape whatever the raw image sizes (DeviceFeed docstring).
+    if files:
+        feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev, ragged=True, decode_workers=args.decode_workers)
+    else:
+        feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev)
     trainer = Trainer(net, levels, optimizer=args.optimizer, learning_rate=args.learning_rate,
                       grad_clip_norm=args.grad_clip_norm, loss_mode=args.loss, device=dev, use_graph=not args.no_graph,
                       input_fn=feed)
@@ -999,9 +1035,10 @@ def main(argv=None):
     loader.skip(drawn0)                                                            # (before the feed's thread draws: it starts lazily)
     broadcast_initial_state(trainer)
     feed.start()
+    t0 = time.perf_counter()
     try:
         for epoch in range(args.epochs):
-            for _ in range(args.steps_per_epoch):
+            for _ in range(steps_per_epoch):
                 out = trainer.step()                                               # batch = [image, hflip] of a new sample
                 step += 1
                 if step % 20 == 0 and rank == 0:
@@ -1014,9 +1051,16 @@ def main(argv=None):
                                 extra={'epochs_done': epoch + 1, 'samples_drawn': drawn0 + feed.samples_staged})
     finally:
         feed.close()
+    # what the run did, for measuring tools (tools/files_bench.py): wall time of the training loop (captures, checkpoints included)
+    LAST_RUN.update(steps=step, seconds=time.perf_counter() - t0, samples=feed.samples_staged, recaptures=trainer.recaptures,
+                    graph_sets=len(trainer._graph_cache))
     if args.eval_images and rank == 0:
-        res = evaluate(net, Shapes(None, image_size=(args.scale + args.scale // 4, args.scale), seed=12345), levels,
-                       args.eval_images, scale=args.scale, device=dev)
+        if args.eval_dataset:
+            from data_loaders.inferred import Inferred
+            eval_loader = Inferred(args.eval_dataset[0], args.eval_dataset[1:])
+        else:
+            eval_loader = Shapes(None, image_size=(args.scale + args.scale // 4, args.scale), seed=12345)
+        res = evaluate(net, eval_loader, levels, args.eval_images, scale=args.scale, device=dev)
         print('eval: mAP %.4f AP50 %.4f AP75 %.4f class_iou %.4f regr_iou %.4f over %d images' % (
             res['mAP'], res['AP50'], res['AP75'], res['class_iou'], res['regr_iou'], res['images']), flush=True)
     if started:
