@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 408
+#define RN_API_VERSION 409
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -505,6 +505,31 @@ typedef struct rn_resize_desc {
 } rn_resize_desc;
 int rn_resize_pair_u8(const uint8_t* raw, int64_t raw_capacity, const rn_resize_desc* desc, float* pair, int oh, int ow,
                       const float* mean, const float* stdv, rn_stream_t stream);
+
+/* rn_resize_pair_u8 with the training-time augmentation the reference names in augment_sample and leaves as a TODO
+ * (dataset.py:206-212: random_contrast(0.8, 1.2), random_brightness(0.2), random_saturation(0.8, 1.0); asked for by
+ * train_input_fn's augment=True, train.py:190-198) plus a crop window, all driven by a DEVICE descriptor uploaded with the
+ * sample: r = the pair's resize of raw[y0:y0+ch, x0:x0+cw] (hs = (ch-1)/(oh-1), ws = (cw-1)/(ow-1) in fp32 from the host, 0
+ * when the output extent is 1);  a = (r - m_c) * f + m_c with m_c the fp64-accumulated channel mean of r;  b = clamp(a + d, 0, 1);
+ * s_c = M - (M - b_c) * min(k, M / (M - n)) with M / n the channel max / min of b (HSV saturation times k, clamped to 1; s = b
+ * when M == n);  then the normalisation and the two slots as in rn_resize_pair_u8.  The full contract is the comment in front
+ * of the kernels (csrc/preprocess.hip).  f == 1 and k == 1 skip their step, so the full window with f = 1, d = 0, k = 1 gives
+ * rn_resize_pair_u8's output bit for bit, and a window alone gives rn_resize_pair_u8 of a contiguous copy of the crop.
+ * Two launches (per-block fp64 channel sums, then the transform), grids a function of (oh, ow) only, no atomics, nothing to
+ * clear between replays: one capture serves every raw size, window and parameter draw, bit-identical run to run.  h and w are
+ * the raw image's size; reads stay inside raw[0, raw_capacity) whatever `desc` holds.
+ * workspace: rn_resize_pair_u8_augment_workspace(oh, ow) bytes, 8-byte aligned (the partial sums). */
+typedef struct rn_augment_desc {
+  int32_t h, w;            /* raw image */
+  int32_t y0, x0, ch, cw;  /* crop window in raw pixels */
+  float hs, ws;            /* the window's resize ratios */
+  float f, d, k;           /* contrast factor (> 0), brightness delta, saturation factor (>= 0) */
+  int32_t reserved;
+} rn_augment_desc;
+size_t rn_resize_pair_u8_augment_workspace(int oh, int ow);
+int rn_resize_pair_u8_augment(const uint8_t* raw, int64_t raw_capacity, const rn_augment_desc* desc, float* pair, int oh, int ow,
+                              const float* mean, const float* stdv, void* workspace, size_t workspace_bytes,
+                              rn_stream_t stream);
 
 /* ------------------------------------------------------------------ loss
  * Replaces utils.process_labels_and_logits/postprocess_and_mask (utils.py:240-284; the

@@ -149,6 +149,33 @@ def resize_pair_u8(raw, desc, size, normalize=True, out=None):
     return pair
 
 
+def augment_desc(hw, values, size):
+    """rn_augment_desc of a raw (h, w) image, augmentation.Draw `values` (crop window y0, x0, ch, cw in raw pixels; contrast f,
+    brightness d, saturation k) and the output size = (oh, ow), as int32 [12] (the floats' fp32 bits): h, w, y0, x0, ch, cw,
+    hs, ws, f, d, k, 0 -- hs / ws are resize_desc's ratios of the WINDOW, bit for bit."""
+    ratios = resize_desc((values.ch, values.cw), size)[2:]
+    fdk = np.array([values.f, values.d, values.k], np.float32).view(np.int32)
+    return np.concatenate([np.array([int(hw[0]), int(hw[1]), values.y0, values.x0, values.ch, values.cw], np.int32), ratios, fdk,
+                           np.zeros(1, np.int32)])
+
+
+def resize_pair_u8_augment(raw, desc, size, normalize=True, out=None):
+    """rn_resize_pair_u8_augment: resize_pair_u8 of the crop window with contrast, brightness and saturation applied (the
+    contract is stated in csrc/preprocess.hip), every parameter read from `desc` (int32 [12] device tensor, augment_desc) at
+    run time -> [2, oh, ow, 3] fp32.  Two launches; the partial channel sums live in the stream's workspace."""
+    oh, ow = int(size[0]), int(size[1])
+    pair = torch.empty((2, oh, ow, 3), dtype=torch.float32, device=raw.device) if out is None else out
+    assert pair.is_contiguous() and tuple(pair.shape) == (2, oh, ow, 3) and pair.dtype == torch.float32
+    assert raw.dtype == torch.uint8 and desc.dtype == torch.int32 and desc.numel() == 12
+    mean = (C.c_float * 3)(*MEAN) if normalize else None
+    std = (C.c_float * 3)(*STD) if normalize else None
+    L_ = _rn.lib()
+    ws = _rn.workspace(L_.rn_resize_pair_u8_augment_workspace(oh, ow), raw.device)
+    _rn.check(L_.rn_resize_pair_u8_augment(_rn.ptr(raw), int(raw.numel()), _rn.ptr(desc), _rn.f32(pair), oh, ow, mean, std,
+                                           ws.data_ptr(), ws.numel(), _rn.stream()), 'rn_resize_pair_u8_augment')
+    return pair
+
+
 def preprocess_image(image):
     """(image - MEAN) / STD (train.py:48-49) for a float image already at its final size."""
     return rescale_image(image, size=tuple(image.shape[-3:-1]), normalize=True)
@@ -228,13 +255,23 @@ def _done(value):
     return f
 
 
-def build_dataset(data_loader, levels, scale=None, shuffle=None, augment=False, device='cuda', normalize=True, decode_workers=4):
+def build_dataset(data_loader, levels, scale=None, shuffle=None, augment=False, device='cuda', normalize=True, decode_workers=4,
+                  first_ordinal=0):
     """Generator form of dataset.py:154-215: per sample  decode -> boxes / image_size -> rescale_image ->
     build_labels -> [sample, hflip(sample)] batch -> preprocess_image.  Everything after the host loader runs on the
-    device (sample_batch).  `shuffle` / `augment` are accepted for signature parity (the reference's augment_sample is a
-    TODO stub; shuffling belongs to the loader here)."""
+    device (sample_batch).  `shuffle` is accepted for signature parity (shuffling belongs to the loader here).
+    augment: False / None, or an augmentation.Policy (the reference's augment_sample, dataset.py:206-212): sample i of the
+    stream is drawn at ordinal first_ordinal + i with the loader's rank and goes through resize_pair_u8_augment, its labels
+    built from the transformed boxes -- what DeviceFeed(ragged=True, augment=policy) stages, eagerly.  uint8 images only.
+    augment=True, the literal the reference's train_input_fn passes (train.py:190-198), stays what it has always been here and
+    is in the reference, whose augment_sample is a stub: accepted, no transform.  Anything else raises a TypeError."""
+    augment = _policy_or_none(augment, allow_true=True)
     dev = torch.device(device)
-    for sample in decoded(data_loader, decode_workers):
+    for i, sample in enumerate(decoded(data_loader, decode_workers)):
+        if augment:
+            yield _augmented_batch(sample, augment, int(getattr(data_loader, 'rank', 0)), int(first_ordinal) + i, levels,
+                                   data_loader.num_classes, scale, normalize, dev)
+            continue
         image = torch.from_numpy(np.ascontiguousarray(sample['image'])).to(dev)                # uint8 or float [H,W,3]
         h, w = int(image.shape[0]), int(image.shape[1])
         boxes = np.asarray(sample['boxes'], np.float32) / np.asarray([h, w, h, w], np.float32)   # dataset.py:163
@@ -243,6 +280,34 @@ def build_dataset(data_loader, levels, scale=None, shuffle=None, augment=False, 
                              normalize=normalize)
         batch.update(boxes=boxes, class_ids=sample['class_ids'])
         yield batch
+
+
+def _policy_or_none(augment, allow_true=False):
+    """None for None / False (and for True where the caller keeps the reference's literal as a no-op), the policy itself for an
+    augmentation.Policy (anything with its `draw`), a TypeError otherwise."""
+    if augment is None or augment is False or (allow_true and augment is True):
+        return None
+    if isinstance(augment, bool) or not callable(getattr(augment, 'draw', None)):
+        raise TypeError("augment must be None, False or an augmentation.Policy, got %r" % (augment,))
+    return augment
+
+
+def _augmented_batch(sample, policy, rank, ordinal, levels, num_classes, scale, normalize, dev):
+    img = np.ascontiguousarray(sample['image'])
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("build_dataset(augment=policy) transforms uint8 [H, W, 3] images (the augmentation kernel reads raw "
+                         "bytes), got %s %s" % (img.dtype, img.shape))
+    h, w = int(img.shape[0]), int(img.shape[1])
+    boxes = np.asarray(sample['boxes'], np.float32).reshape(-1, 4) / np.asarray([h, w, h, w], np.float32)   # dataset.py:163
+    values, boxes, ids = policy.draw(rank, ordinal, (h, w), boxes, np.asarray(sample['class_ids'], np.int32).reshape(-1))
+    size = rescale_size((h, w), scale) if scale is not None else (h, w)
+    desc = augment_desc((h, w), values, size)
+    pair = resize_pair_u8_augment(torch.from_numpy(img.reshape(-1)).to(dev), torch.from_numpy(desc).to(dev), size,
+                                  normalize=normalize)
+    c, r, m = build_labels(size, torch.from_numpy(np.asarray(ids, np.int32)).to(dev)[None], torch.from_numpy(boxes).to(dev)[None],
+                           levels, num_classes, flip_pair=True)
+    return {'image': pair, 'image_size': size, 'detection': {'classifications': c, 'regressions': r}, 'trainable_masks': m,
+            'boxes': boxes, 'class_ids': ids, 'augment_desc': desc}
 
 
 class DeviceFeed(object):
@@ -262,17 +327,28 @@ class DeviceFeed(object):
     `max_objects()` hints (objects rounded up to 32); without hints the capacity grows x1.5 when a sample needs more, and each
     growth is a new generation.  `features()` is rn_resize_pair_u8 (raw size read from the descriptor at run time) + the
     paired assignment, so the shape key is (oh, ow, object capacity, generation): one captured graph per NETWORK INPUT shape,
-    whatever raw sizes map to it.  'image_file' samples are decoded by `decode_workers` threads (`decoded`)."""
+    whatever raw sizes map to it.  'image_file' samples are decoded by `decode_workers` threads (`decoded`).
+
+    augment=policy (an augmentation.Policy; ragged mode only): the loader thread draws sample i's parameters at ordinal
+    first_ordinal + i (rank: the loader's), writes the rn_augment_desc and the TRANSFORMED boxes / ids into the pinned slot, and
+    `features()` is rn_resize_pair_u8_augment + the paired assignment.  Every parameter reaches the kernels through the uploaded
+    descriptor, so the shape key -- and with it the set of captured graphs -- is the same as without a policy.  `last_sample`
+    carries the transformed boxes and the descriptor ('augment_desc').  augment=None / False: the path above, untouched."""
 
     def __init__(self, data_loader, levels, scale=None, device='cuda', max_obj=32, normalize=True, prefetch=3, ragged=False,
-                 decode_workers=4):
+                 decode_workers=4, augment=None, first_ordinal=0):
         import queue
         import threading
+        self.augment = _policy_or_none(augment)        # (checked before anything touches the device)
+        if self.augment is not None and not ragged:
+            raise ValueError("DeviceFeed(augment=policy) needs ragged=True: the augmentation kernel reads the raw uint8 image")
         self.levels, self.scale, self.normalize = levels, scale, normalize
         self.num_classes = data_loader.num_classes
         self.device = torch.device(device)
         self.max_obj = int(max_obj)
         self.ragged = bool(ragged)
+        self._rank = int(getattr(data_loader, 'rank', 0))
+        self._ordinal = int(first_ordinal)
         if self.ragged:
             self._it = iter(decoded(data_loader, decode_workers))
             px = getattr(data_loader, 'max_image_pixels', None)
@@ -359,6 +435,11 @@ class DeviceFeed(object):
                     self._obj_cap = max(self._obj_cap, -(-len(ids) // 32) * 32)
                     self._generation += 1
                 oh, ow = rescale_size((h, w), self.scale) if self.scale is not None else (h, w)
+                info = {}
+                if self.augment is not None:
+                    values, boxes, ids = self.augment.draw(self._rank, self._ordinal, (h, w), boxes, ids)
+                    self._ordinal += 1
+                    info['augment_desc'] = augment_desc((h, w), values, (oh, ow))
                 host = slot[0] if slot is not None else None
                 if host is None or host['gen'] != self._generation:
                     host = {'gen': self._generation,
@@ -367,14 +448,18 @@ class DeviceFeed(object):
                             'boxes': torch.zeros((1, self._obj_cap, 4), dtype=torch.float32).pin_memory(),
                             'ids': torch.zeros((1, self._obj_cap), dtype=torch.int32).pin_memory(),
                             'nobj': torch.zeros((1,), dtype=torch.int32).pin_memory()}
+                    if self.augment is not None:
+                        host['adesc'] = torch.zeros((12,), dtype=torch.int32).pin_memory()
                 host['raw'].numpy()[:img.size] = img.reshape(-1)
                 host['desc'].numpy()[:] = resize_desc((h, w), (oh, ow))
+                if self.augment is not None:
+                    host['adesc'].numpy()[:] = info['augment_desc']
                 host['boxes'].zero_(); host['ids'].zero_()
                 host['boxes'].numpy()[0, :len(ids)] = boxes
                 host['ids'].numpy()[0, :len(ids)] = ids
                 host['nobj'][0] = len(ids)
                 host['bytes'], host['size'] = img.size, (oh, ow)
-                self._ready.put((host, {'boxes': boxes, 'class_ids': ids, 'image_hw': (h, w)}))
+                self._ready.put((host, dict(info, boxes=boxes, class_ids=ids, image_hw=(h, w))))
             self._ready.put(None)
         except BaseException as e:
             self._error = e
@@ -398,7 +483,7 @@ class DeviceFeed(object):
         with torch.cuda.stream(cs):
             n = host['bytes']
             self._static['raw'][:n].copy_(host['raw'][:n], non_blocking=True)
-            for k in ('desc', 'boxes', 'ids', 'nobj'):
+            for k in ('desc', 'boxes', 'ids', 'nobj') + (('adesc',) if 'adesc' in host else ()):
                 self._static[k].copy_(host[k], non_blocking=True)
             done = torch.cuda.Event()
             done.record(cs)
@@ -408,7 +493,10 @@ class DeviceFeed(object):
     def _features_ragged(self):
         s = self._static
         oh, ow = self._size
-        pair = resize_pair_u8(s['raw'], s['desc'], (oh, ow), normalize=self.normalize)
+        if self.augment is not None:
+            pair = resize_pair_u8_augment(s['raw'], s['adesc'], (oh, ow), normalize=self.normalize)
+        else:
+            pair = resize_pair_u8(s['raw'], s['desc'], (oh, ow), normalize=self.normalize)
         c, r, m = build_labels((oh, ow), s['ids'], s['boxes'], self.levels, self.num_classes, num_obj=s['nobj'], flip_pair=True)
         return {'image': pair, 'image_size': (oh, ow), 'detection': {'classifications': c, 'regressions': r}, 'trainable_masks': m}
 

@@ -935,6 +935,12 @@ def build_parser():
     parser.add_argument('--eval-images', type=int, default=0, help='after training: mAP / IoU metrics over this many samples')
     parser.add_argument('--eval-dataset', type=str, nargs='+', default=None,
                         help='TYPE ARGS... as --dataset; required with --eval-images for a file dataset')
+    parser.add_argument('--augment', action='store_true',
+                        help='file datasets: random contrast (0.8, 1.2), brightness 0.2, saturation (0.8, 1.0) per training sample '
+                             '(dataset.py:206-212), on the device inside the step; the evaluation loader never augments')
+    parser.add_argument('--augment-crop', type=float, default=None, metavar='S',
+                        help='with --augment: also a random crop of side fraction U[S, 1] (0 < S <= 1), boxes clipped to it')
+    parser.add_argument('--augment-seed', type=int, default=None, metavar='N', help='with --augment: seed of the draws (default 0)')
     parser.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of replaying the captured step')
     return parser
 
@@ -988,6 +994,12 @@ def main(argv=None):
         parser.error('--dataset: shapes [PATH NUM SIZE] | pascal ROOT SUBSET | coco ANN_JSON IMAGES_DIR (got %s)' % ' '.join(args.dataset))
     if files and args.eval_images and not args.eval_dataset:
         parser.error('--eval-images with a file dataset needs --eval-dataset TYPE ARGS...')
+    if (args.augment or args.augment_crop is not None or args.augment_seed is not None) and not files:
+        parser.error('--augment transforms raw uint8 image files: it needs --dataset pascal ... or coco ...')
+    if (args.augment_crop is not None or args.augment_seed is not None) and not args.augment:
+        parser.error('--augment-crop / --augment-seed need --augment')
+    if args.augment_crop is not None and not (0.0 < args.augment_crop <= 1.0):
+        parser.error('--augment-crop S: 0 < S <= 1 (got %g)' % args.augment_crop)
     dev, rank, world, started = init_distributed()
     from data_loaders.shapes import Shapes
     # every replica draws its own samples (dataset.py:182-204: a replica's batch is [sample, hflip(sample)])
@@ -1014,7 +1026,21 @@ def main(argv=None):
     # static device buffers; rescale, normalisation, the h-flip and the anchor assignment of every NEW sample run inside the
     # captured step (one hipGraph per backward segment, replayed per step; --no-graph launches the same kernels eagerly).
     # File datasets: ragged staging, one graph set per network input shape whatever the raw image sizes (DeviceFeed docstring).
-    if files:
+    # --augment: the sample's crop window and photometric scalars are drawn on the loader thread as a function of (seed, rank,
+    # position in the stream) and reach the kernels through a descriptor uploaded with the sample: the same graphs serve every draw
+    drawn0 = 0
+    path = None if args.experiment is None else os.path.join(args.experiment, 'model.safetensors')
+    if path is not None and os.path.exists(path):
+        drawn0 = int(checkpoint.load_extra(path).get('samples_drawn', 0))
+    # (first_ordinal = samples_drawn holds because every staged sample is one sample of the loader's stream: the file readers drop
+    # invalid records once, up front, so Inferred skips nothing while iterating -- checked where the checkpoint is written)
+    skipped0 = getattr(loader, 'skipped', 0)
+    if files and args.augment:
+        import augmentation
+        policy = augmentation.Policy(crop_min=1.0 if args.augment_crop is None else args.augment_crop, seed=args.augment_seed or 0)
+        feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev, ragged=True, decode_workers=args.decode_workers,
+                                  augment=policy, first_ordinal=drawn0)
+    elif files:
         feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev, ragged=True, decode_workers=args.decode_workers)
     else:
         feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev)
@@ -1022,14 +1048,12 @@ def main(argv=None):
                       grad_clip_norm=args.grad_clip_norm, loss_mode=args.loss, device=dev, use_graph=not args.no_graph,
                       input_fn=feed)
     step = 0
-    drawn0 = 0
-    path = None if args.experiment is None else os.path.join(args.experiment, 'model.safetensors')
     if path is not None and os.path.exists(path):
         step = checkpoint.load(path, net, trainer)                                 # every rank reads the same file
         # like the reference (train.py:271-273: `for epoch in range(args.epochs): estimator.train(...)` on a restored global
         # step) a rerun trains args.epochs MORE epochs; what is carried over besides the weights: the step count, the
-        # optimizer slots, the dropout counter and the position in the sample stream (counted in samples, not steps)
-        drawn0 = int(checkpoint.load_extra(path).get('samples_drawn', 0))
+        # optimizer slots, the dropout counter and the position in the sample stream (counted in samples, not steps: drawn0
+        # above, which is also the ordinal the augmentation draws continue from)
         if rank == 0:
             print('restored step', step)
     loader.skip(drawn0)                                                            # (before the feed's thread draws: it starts lazily)
@@ -1046,6 +1070,9 @@ def main(argv=None):
                         epoch, step, out['class_loss'].item(), out['regr_loss'].item(), out['regularization_loss'].item()),
                         flush=True)
             trainer.check_device_errors()
+            if args.augment and getattr(loader, 'skipped', 0) != skipped0:
+                raise _rn.RnError("the loader skipped samples while iterating: the augmentation's ordinals no longer equal the "
+                                  "stream position a checkpoint stores (samples_drawn)")
             if path is not None and rank == 0:                                     # replicas are identical: rank 0 writes
                 checkpoint.save(path, net, trainer, step=step,
                                 extra={'epochs_done': epoch + 1, 'samples_drawn': drawn0 + feed.samples_staged})

@@ -3,7 +3,10 @@ of other sizes) into DIR, trains through train.main with --shape-runs 0 and 8, a
 images/s (two per step: [image, hflip]), recaptures per 100 steps, the host decode rate of one worker, and the in-memory
 shapes stream at the same --scale.  The training times are wall time of train.main's loop, graph captures included.
 
-    python tools/files_bench.py DIR [--images 96] [--steps 200] [--scale 512] [--decode-workers 4]
+    python tools/files_bench.py DIR [--images 96] [--steps 200] [--scale 512] [--decode-workers 4] [--shape-runs 0 8] [--augment [S]]
+
+--augment [S]: the file runs train with --augment (and --augment-crop S when S is given): the cost of the augmentation kernels and of
+the loader thread's draws shows as the difference to a run without it.
 """
 import argparse
 import json
@@ -46,6 +49,9 @@ def main():
     ap.add_argument('--scale', type=int, default=512)
     ap.add_argument('--decode-workers', type=int, default=4)
     ap.add_argument('--backbone', default='mobilenet_v2')
+    ap.add_argument('--shape-runs', type=int, nargs='+', default=[0, 8])
+    ap.add_argument('--augment', type=float, nargs='?', const=1.0, default=None, metavar='S')
+    ap.add_argument('--no-shapes', action='store_true', help='skip the in-memory shapes stream')
     a = ap.parse_args()
     import dataset
     sizes, names = write_dataset(a.dir, a.images)
@@ -57,11 +63,15 @@ def main():
     print(json.dumps({'what': 'decode', 'images': len(files), 'images_per_s_per_worker': round(len(files) / dt, 1),
                       'network_sizes': len({dataset.rescale_size(s, a.scale) for s in sizes})}), flush=True)
     common = ['--scale', str(a.scale), '--steps-per-epoch', str(a.steps), '--backbone', a.backbone, '--dropout', '0.0']
-    for k in (0, 8):
-        r = run(['--dataset', 'pascal', a.dir, 'trainval', '--shape-runs', str(k), '--decode-workers', str(a.decode_workers)] + common)
-        print(json.dumps(dict(what='pascal', shape_runs=k, **r)), flush=True)
-    r = run(['--dataset', 'shapes'] + common)
-    print(json.dumps(dict(what='shapes', **r)), flush=True)
+    aug = []
+    if a.augment is not None:
+        aug = ['--augment'] + (['--augment-crop', str(a.augment)] if a.augment < 1.0 else [])
+    for k in a.shape_runs:
+        r = run(['--dataset', 'pascal', a.dir, 'trainval', '--shape-runs', str(k), '--decode-workers', str(a.decode_workers)] + common + aug)
+        print(json.dumps(dict(what='pascal', shape_runs=k, augment=a.augment, **r)), flush=True)
+    if not a.no_shapes:
+        r = run(['--dataset', 'shapes'] + common)
+        print(json.dumps(dict(what='shapes', **r)), flush=True)
 
 
 if __name__ == '__main__':
