@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 409
+#define RN_API_VERSION 410
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -530,6 +530,29 @@ size_t rn_resize_pair_u8_augment_workspace(int oh, int ow);
 int rn_resize_pair_u8_augment(const uint8_t* raw, int64_t raw_capacity, const rn_augment_desc* desc, float* pair, int oh, int ow,
                               const float* mean, const float* stdv, void* workspace, size_t workspace_bytes,
                               rn_stream_t stream);
+
+/* Several samples per step (dataset.py:145-151 rescale, 182-204 [image, hflip] and the batch of samples the reference's
+ * tf.data pipeline would form, train.py:48-49 preprocess_image): rn_resize_pair_u8 of k raw images in ONE launch.  Raw image i
+ * starts at raw + i * sample_stride_bytes and has the DEVICE descriptor desc[i]; pairs [2k, oh, ow, 3] fp32 gets
+ * pairs[2i] = the rescaled + normalised sample i and pairs[2i+1] = its h-flip, bit for bit what rn_resize_pair_u8(raw + i * stride,
+ * stride, desc + i, pairs + 2i * oh*ow*3, ...) writes: the same arithmetic in the same order, the grid is (that call's blocks,
+ * sample).  All raw sizes are read from the descriptors at run time: one capture serves every group of k raw sizes that map to
+ * (oh, ow).  sample_stride_bytes is every sample's raw_capacity: reads of sample i stay inside its own slot
+ * raw[i * stride, (i+1) * stride) whatever desc[i] holds (a descriptor with h*w*3 > stride gives wrong pixels, never a read
+ * of the next slot or past the buffer).  1 <= k <= 65535. */
+int rn_resize_pair_u8_batch(const uint8_t* raw, int64_t sample_stride_bytes, const rn_resize_desc* desc, int k, float* pairs,
+                            int oh, int ow, const float* mean, const float* stdv, rn_stream_t stream);
+
+/* rn_resize_pair_u8_augment of k raw images (dataset.py:206-212 augment_sample per sample, then the calls above), laid out as for
+ * rn_resize_pair_u8_batch with desc[i] an rn_augment_desc.  TWO launches whatever k is: the per-block fp64 channel sums of every
+ * sample (sample i's in its own part of the workspace), then the transform of every sample from its own sums -- nothing is added
+ * across samples, no atomics, nothing to clear between replays.  Slots 2i / 2i+1 are bit for bit rn_resize_pair_u8_augment's of
+ * sample i alone.  workspace: rn_resize_pair_u8_augment_batch_workspace(k, oh, ow) bytes (k times the single-image query),
+ * 8-byte aligned. */
+size_t rn_resize_pair_u8_augment_batch_workspace(int k, int oh, int ow);
+int rn_resize_pair_u8_augment_batch(const uint8_t* raw, int64_t sample_stride_bytes, const rn_augment_desc* desc, int k,
+                                    float* pairs, int oh, int ow, const float* mean, const float* stdv, void* workspace,
+                                    size_t workspace_bytes, rn_stream_t stream);
 
 /* ------------------------------------------------------------------ loss
  * Replaces utils.process_labels_and_logits/postprocess_and_mask (utils.py:240-284; the

@@ -19,7 +19,7 @@ LOSS_MODE = {"bce_dice": 0, "focal": 1}
 OPT = {"momentum": 0, "rmsprop": 1, "adam": 2}
 OPT_BLOCK = 1024
 LOSS_STATS_HEADER = 8
-API_VERSION = 409        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 410        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -175,6 +175,7 @@ SYMBOLS = [
     "rn_conv3x3_winograd_bwd_workspace", "rn_conv3x3_winograd_bwd", "rn_flush_reductions", "rn_gemm_batched",
     "rn_winograd_bwd_products_workspace", "rn_winograd_bwd_products", "rn_wino_gn_rows", "rn_conv3x3_winograd_gn", "rn_conv3x3_winograd_gn_bwd", "rn_conv3x3_winograd_gn_bwd_wgrad", "rn_reduce_rows", "rn_resize_bilinear_normalize", "rn_resize_pair_u8",
     "rn_resize_pair_u8_augment_workspace", "rn_resize_pair_u8_augment",
+    "rn_resize_pair_u8_batch", "rn_resize_pair_u8_augment_batch_workspace", "rn_resize_pair_u8_augment_batch",
     "rn_dwgn_supported", "rn_dwgn_fwd", "rn_dwgn_bwd", "rn_depthwise_fwd", "rn_depthwise_dgrad", "rn_depthwise_wgrad_workspace", "rn_depthwise_wgrad", "rn_depthwise_bwd",
     "rn_group_norm_sync_bytes", "rn_group_norm_workspace", "rn_group_norm_fwd", "rn_group_norm_bwd",
     "rn_act_fwd", "rn_act_bwd", "rn_upsample_add_fwd", "rn_upsample_add_bwd_top",
@@ -256,6 +257,12 @@ def lib():
         L.rn_resize_pair_u8_augment_workspace.restype = C.c_size_t
         L.rn_resize_pair_u8_augment.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rn_resize_pair_u8_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+        L.rn_resize_pair_u8_augment_batch_workspace.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.rn_resize_pair_u8_augment_batch_workspace.restype = C.c_size_t
+        L.rn_resize_pair_u8_augment_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rn_gemm_batched.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]
         L.rn_flush_reductions.argtypes = [C.c_void_p, C.c_void_p]
         L.rn_conv3x3_winograd_wgrad_workspace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]

@@ -83,12 +83,13 @@ __device__ __forceinline__ float fetch_u8(const uint8_t* raw, int64_t cap, int64
   return (idx >= 0 && idx < cap) ? (float)raw[idx] * (1.0f / 255.0f) : 0.0f;  // convert_image_dtype
 }
 
-__global__ __launch_bounds__(256) void resize_pair_u8_kernel(const PairArgs a) {
+// the pair of ONE sample, by the blocks (bx of nbx) that share it: the single-image kernel and the batched one run this body
+__device__ __forceinline__ void resize_pair_u8_body(const PairArgs& a, unsigned bx, unsigned nbx) {
   const int h = a.desc->h, w = a.desc->w;
   const float hs = a.desc->hs, ws = a.desc->ws;
   const int64_t total = (int64_t)a.oh * a.ow;
   const int64_t plane = total * 3;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+  for (int64_t i = (int64_t)bx * 256 + threadIdx.x; i < total; i += (int64_t)nbx * 256) {
     const int ox = (int)(i % a.ow), oy = (int)(i / a.ow);
     const float iny = (float)oy * hs, inx = (float)ox * ws;
     const float fy = floorf(iny), fx = floorf(inx);
@@ -113,6 +114,22 @@ __global__ __launch_bounds__(256) void resize_pair_u8_kernel(const PairArgs a) {
     }
   }
 }
+
+__global__ __launch_bounds__(256) void resize_pair_u8_kernel(const PairArgs a) { resize_pair_u8_body(a, blockIdx.x, gridDim.x); }
+
+// K samples in one launch, grid (output pixel blocks of one sample, sample): sample i is a PairArgs of its own -- raw slot i of
+// `cap` bytes (the slot stride, which is also its read bound), descriptor i, slots 2i / 2i+1 of the output -- run through the
+// single-image body.
+__global__ __launch_bounds__(256) void resize_pair_u8_batch_kernel(const PairArgs first) {
+  const int64_t s = blockIdx.y;
+  PairArgs a = first;
+  a.raw += s * a.cap;
+  a.desc += s;
+  a.y += s * 2 * ((int64_t)a.oh * a.ow * 3);
+  resize_pair_u8_body(a, blockIdx.x, gridDim.x);
+}
+
+constexpr int PAIR_BATCH_MAX = 65535;   // samples per launch: gridDim.y
 }  // namespace
 
 extern "C" int rn_resize_pair_u8(const uint8_t* raw, int64_t raw_capacity, const rn_resize_desc* desc, float* pair, int oh,
@@ -127,6 +144,23 @@ extern "C" int rn_resize_pair_u8(const uint8_t* raw, int64_t raw_capacity, const
   int64_t b = (total + 255) / 256;
   if (b > 16384) b = 16384;
   hipLaunchKernelGGL(resize_pair_u8_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, a);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
+}
+
+extern "C" int rn_resize_pair_u8_batch(const uint8_t* raw, int64_t sample_stride_bytes, const rn_resize_desc* desc, int k,
+                                       float* pairs, int oh, int ow, const float* mean, const float* stdv, rn_stream_t stream) {
+  RN_CHECK_ARG(raw && desc && pairs && sample_stride_bytes >= 3 && oh >= 1 && ow >= 1, "resize_pair_u8_batch: bad argument");
+  RN_CHECK_ARG(k >= 1 && k <= PAIR_BATCH_MAX, "resize_pair_u8_batch: k = %d (1 .. %d samples)", k, PAIR_BATCH_MAX);
+  RN_CHECK_ARG((mean == nullptr) == (stdv == nullptr), "resize_pair_u8_batch: mean and std go together");
+  PairArgs a = {};
+  a.raw = raw; a.cap = sample_stride_bytes; a.desc = desc; a.y = pairs; a.oh = oh; a.ow = ow;
+  a.normalize = mean ? 1 : 0;
+  for (int i = 0; i < 3 && mean; ++i) { a.mean[i] = mean[i]; a.stdv[i] = stdv[i]; }
+  const int64_t total = (int64_t)oh * ow;
+  int64_t b = (total + 255) / 256;      // per sample: the single-image grid, so every thread meets the pixels it meets there
+  if (b > 16384) b = 16384;
+  hipLaunchKernelGGL(resize_pair_u8_batch_kernel, dim3((unsigned)b, (unsigned)k), dim3(256), 0, (hipStream_t)stream, a);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }
@@ -196,10 +230,10 @@ __device__ __forceinline__ void aug_resized(const AugArgs& a, int oy, int ox, fl
 
 // (measured 11.0 us at 375 x 500 -> 512 x 683 with these 256-thread blocks, profiles/augment_cost.txt; larger blocks for the
 // <= AUG_MAX_BLOCKS ranges are untried)
-__global__ __launch_bounds__(AUG_STATS_THREADS) void augment_stats_kernel(const AugArgs a) {
+__device__ __forceinline__ void augment_stats_body(const AugArgs& a, unsigned bx) {
   __shared__ double red[3][AUG_STATS_THREADS];
   const int64_t total = (int64_t)a.oh * a.ow;
-  const int64_t lo = (int64_t)blockIdx.x * a.ppb;
+  const int64_t lo = (int64_t)bx * a.ppb;
   const int64_t hi = min(lo + a.ppb, total);
   if (a.desc->f == 1.0f) return;         // (uniform) no contrast: the apply pass does not read the sums
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -217,10 +251,12 @@ __global__ __launch_bounds__(AUG_STATS_THREADS) void augment_stats_kernel(const 
     }
     __syncthreads();
   }
-  if (threadIdx.x < 3) a.partial[(int64_t)blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0];
+  if (threadIdx.x < 3) a.partial[(int64_t)bx * 3 + threadIdx.x] = red[threadIdx.x][0];
 }
 
-__global__ __launch_bounds__(256) void augment_apply_kernel(const AugArgs a) {
+__global__ __launch_bounds__(AUG_STATS_THREADS) void augment_stats_kernel(const AugArgs a) { augment_stats_body(a, blockIdx.x); }
+
+__device__ __forceinline__ void augment_apply_body(const AugArgs& a, unsigned bx, unsigned nbx) {
   __shared__ double part[3 * AUG_MAX_BLOCKS];
   __shared__ float mean_c[3];
   const int64_t total = (int64_t)a.oh * a.ow;
@@ -236,7 +272,7 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const AugArgs a) {
     __syncthreads();
   }
   const int64_t plane = total * 3;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+  for (int64_t i = (int64_t)bx * 256 + threadIdx.x; i < total; i += (int64_t)nbx * 256) {
     const int ox = (int)(i % a.ow), oy = (int)(i / a.ow);
     float v[3];
     aug_resized(a, oy, ox, v);
@@ -265,6 +301,28 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const AugArgs a) {
       o1[c] = u;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void augment_apply_kernel(const AugArgs a) { augment_apply_body(a, blockIdx.x, gridDim.x); }
+
+// K samples per launch, grids (blocks of one sample, sample): sample i is an AugArgs of its own -- raw slot i of `cap` bytes,
+// descriptor i, its own nblk partial sums, slots 2i / 2i+1 -- run through the single-image bodies.  The sums of a sample are
+// formed by its own stats blocks and read by its own apply blocks only: nothing is added across samples.
+__device__ __forceinline__ AugArgs aug_sample(const AugArgs& first, int64_t s) {
+  AugArgs a = first;
+  a.raw += s * a.cap;
+  a.desc += s;
+  a.partial += s * 3 * a.nblk;
+  a.y += s * 2 * ((int64_t)a.oh * a.ow * 3);
+  return a;
+}
+
+__global__ __launch_bounds__(AUG_STATS_THREADS) void augment_stats_batch_kernel(const AugArgs first) {
+  augment_stats_body(aug_sample(first, blockIdx.y), blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void augment_apply_batch_kernel(const AugArgs first) {
+  augment_apply_body(aug_sample(first, blockIdx.y), blockIdx.x, gridDim.x);
 }
 
 // stats blocks of (oh, ow): 1024 pixels each (four strides of a block's 256 threads), or -- beyond AUG_MAX_BLOCKS of those --
@@ -304,6 +362,37 @@ extern "C" int rn_resize_pair_u8_augment(const uint8_t* raw, int64_t raw_capacit
   int64_t b = (total + 255) / 256;
   if (b > 16384) b = 16384;
   hipLaunchKernelGGL(augment_apply_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, a);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
+}
+
+extern "C" size_t rn_resize_pair_u8_augment_batch_workspace(int k, int oh, int ow) {
+  if (k < 1 || k > PAIR_BATCH_MAX) return 0;
+  return (size_t)k * rn_resize_pair_u8_augment_workspace(oh, ow);
+}
+
+extern "C" int rn_resize_pair_u8_augment_batch(const uint8_t* raw, int64_t sample_stride_bytes, const rn_augment_desc* desc, int k,
+                                               float* pairs, int oh, int ow, const float* mean, const float* stdv, void* workspace,
+                                               size_t workspace_bytes, rn_stream_t stream) {
+  RN_CHECK_ARG(raw && desc && pairs && workspace && sample_stride_bytes >= 3 && oh >= 1 && ow >= 1,
+               "resize_pair_u8_augment_batch: bad argument");
+  RN_CHECK_ARG(k >= 1 && k <= PAIR_BATCH_MAX, "resize_pair_u8_augment_batch: k = %d (1 .. %d samples)", k, PAIR_BATCH_MAX);
+  RN_CHECK_ARG((mean == nullptr) == (stdv == nullptr), "resize_pair_u8_augment_batch: mean and std go together");
+  RN_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && workspace_bytes >= rn_resize_pair_u8_augment_batch_workspace(k, oh, ow),
+               "resize_pair_u8_augment_batch: workspace of %zu bytes, need %zu (8-byte aligned)", workspace_bytes,
+               rn_resize_pair_u8_augment_batch_workspace(k, oh, ow));
+  AugArgs a = {};
+  a.raw = raw; a.cap = sample_stride_bytes; a.desc = desc; a.y = pairs; a.partial = (double*)workspace; a.oh = oh; a.ow = ow;
+  aug_geometry(oh, ow, &a.nblk, &a.ppb);
+  a.normalize = mean ? 1 : 0;
+  for (int i = 0; i < 3 && mean; ++i) { a.mean[i] = mean[i]; a.stdv[i] = stdv[i]; }
+  hipLaunchKernelGGL(augment_stats_batch_kernel, dim3((unsigned)a.nblk, (unsigned)k), dim3(AUG_STATS_THREADS), 0,
+                     (hipStream_t)stream, a);
+  RN_LAUNCH_CHECK();
+  const int64_t total = (int64_t)oh * ow;
+  int64_t b = (total + 255) / 256;      // per sample: the single-image grid
+  if (b > 16384) b = 16384;
+  hipLaunchKernelGGL(augment_apply_batch_kernel, dim3((unsigned)b, (unsigned)k), dim3(256), 0, (hipStream_t)stream, a);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }

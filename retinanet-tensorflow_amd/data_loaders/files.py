@@ -13,6 +13,13 @@ A reader parses its annotations once into a list of records -- {'image_file', 'b
     input size (dataset.rescale_size of the annotated size -- nothing is decoded), cut into chunks of <= K same-size samples,
     and the chunk order is shuffled with a seed.  Consecutive steps then mostly share one input shape, so a graph-captured
     step replays instead of re-capturing; every sample still appears once per epoch.  K = 0: the plain permutation.
+  * group=K (with scale; for dataset.DeviceFeed(samples_per_step=K), which trains on up to K consecutive samples of one
+    network input size per step): the rank's sequence is cut into the same windows, and every window emits FULL groups of K
+    same-size samples, in an order shuffled with the window's seed.  What is left of a size class -- fewer than K samples --
+    is carried into the next window's pool, where it is taken first; only the end of the epoch emits partial groups, at most
+    one per size class.  Every sample still appears once per epoch.  With group > 0 the order is the grouped one whatever
+    shape_runs says (group wins): runs of one shape are then runs of groups only by chance, so a graph set is re-used through
+    the trainer's cache rather than by adjacency.  `epoch_steps` counts the steps the feed makes of an epoch.
 
 The stream position (`drawn`) is advanced by iteration and by `skip(n)`; an iterator starts where the position is.  With
 repeat=True the stream runs on across epochs without end (training); otherwise it stops at the end of the current epoch.
@@ -40,6 +47,19 @@ def shape_run_order(keys, k, seed):
     return [chunks[j] for j in perm]
 
 
+def greedy_groups(keys, k):
+    """Sizes of the groups dataset.DeviceFeed(samples_per_step=k) forms from a stream with these size keys: the next sample
+    plus those that follow it while they have its key, k at most."""
+    sizes, i, n = [], 0, len(keys)
+    while i < n:
+        j = i + 1
+        while j < n and j - i < k and keys[j] == keys[i]:
+            j += 1
+        sizes.append(j - i)
+        i = j
+    return sizes
+
+
 class FileDataset(Base):
     """Base of the annotation-file readers: subclasses fill `self._records` and `self._class_names`."""
 
@@ -61,12 +81,16 @@ class FileDataset(Base):
     def __len__(self):
         return len(self._records)
 
-    def configure(self, seed=None, rank=0, world=1, shape_runs=0, scale=None, repeat=False):
-        """Set the epoch order (see the module docstring); resets the cached orders, not the stream position."""
+    def configure(self, seed=None, rank=0, world=1, shape_runs=0, scale=None, repeat=False, group=0):
+        """Set the epoch order (see the module docstring); resets the cached orders, not the stream position.  group > 0 decides
+        the order alone: shape_runs is then not applied."""
         assert 0 <= rank < world
         assert shape_runs == 0 or scale is not None, "shape runs group by network input size: they need the scale"
+        assert group == 0 or scale is not None, "groups are formed by network input size: they need the scale"
+        assert group >= 0
         self.seed, self.rank, self.world = seed, int(rank), int(world)
         self.shape_runs, self.scale, self.repeat = int(shape_runs), scale, bool(repeat)
+        self.group = int(group)
         self._epoch_cache = {}
         return self
 
@@ -85,11 +109,57 @@ class FileDataset(Base):
     def max_image_pixels(self):
         return max([int(r['image_size'][0]) * int(r['image_size'][1]) for r in self._records] or [0])
 
+    def _size_key(self, index):
+        import dataset
+        return dataset.rescale_size(self._records[index]['image_size'], self.scale)
+
+    def _group_order(self, epoch, rank):
+        """epoch_order with group > 0, of any rank, uncached: a pure function of (seed, epoch, rank, world, scale, group)."""
+        n = len(self._records)
+        if self.seed is None:
+            perm = np.arange(n)
+        else:
+            perm = np.random.default_rng([int(self.seed), int(epoch)]).permutation(n)
+        mine = [int(i) for i in perm[rank::self.world]]
+        out, carried = [], {}                     # size key -> indices left over from earlier windows (fewer than `group`)
+        for w0 in range(0, len(mine), WINDOW):
+            pool = {}
+            for i in mine[w0:w0 + WINDOW]:
+                pool.setdefault(self._size_key(i), []).append(i)
+            groups = []
+            for key in sorted(set(pool) | set(carried)):
+                members = carried.pop(key, []) + pool.get(key, [])            # carried samples are taken first
+                full = len(members) // self.group * self.group
+                groups += [members[g:g + self.group] for g in range(0, full, self.group)]
+                if full < len(members):
+                    carried[key] = members[full:]
+            seed = [int(self.seed or 0), int(epoch), rank, w0 // WINDOW]
+            for j in np.random.default_rng(seed).permutation(len(groups)):
+                out.extend(groups[j])
+        for key in sorted(carried):               # the end of the epoch: at most one partial group per size class
+            out.extend(carried[key])
+        return out
+
+    def epoch_steps(self, epoch, rank=None):
+        """Steps dataset.DeviceFeed(samples_per_step=group) makes of epoch `epoch` on `rank` (default: this rank): the number of
+        groups it forms greedily from that rank's epoch order (one per sample with group <= 1).  Index arithmetic on the
+        annotated sizes: nothing is read or decoded, and every rank can compute it for every other."""
+        rank = self.rank if rank is None else int(rank)
+        assert 0 <= rank < self.world
+        if self.group <= 1:
+            return len(range(rank, len(self._records), self.world))
+        order = self.epoch_order(epoch) if rank == self.rank else self._group_order(epoch, rank)
+        return len(greedy_groups([self._size_key(i) for i in order], self.group))
+
     def epoch_order(self, epoch):
         """Record indices of epoch `epoch` on this rank, in stream order."""
         got = self._epoch_cache.get(epoch)
         if got is not None:
             return got
+        if self.group > 0:
+            mine = self._group_order(epoch, self.rank)
+            self._epoch_cache = {epoch: mine}
+            return mine
         n = len(self._records)
         if self.seed is None:
             perm = np.arange(n)

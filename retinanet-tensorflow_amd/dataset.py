@@ -176,6 +176,47 @@ def resize_pair_u8_augment(raw, desc, size, normalize=True, out=None):
     return pair
 
 
+def _batch_args(raw, descs, width, size, stride, out):
+    """Checked (k, pairs) of the batched preprocess calls: descs [k, width] int32, raw at least k * stride bytes."""
+    oh, ow = int(size[0]), int(size[1])
+    stride = int(stride)
+    assert raw.dtype == torch.uint8 and raw.is_contiguous() and descs.dtype == torch.int32 and descs.is_contiguous()
+    assert descs.dim() == 2 and descs.shape[1] == width and descs.shape[0] >= 1
+    k = int(descs.shape[0])
+    assert stride >= 3 and int(raw.numel()) >= k * stride, "raw holds %d bytes, %d samples of stride %d need %d" % (
+        raw.numel(), k, stride, k * stride)
+    pairs = torch.empty((2 * k, oh, ow, 3), dtype=torch.float32, device=raw.device) if out is None else out
+    assert pairs.is_contiguous() and tuple(pairs.shape) == (2 * k, oh, ow, 3) and pairs.dtype == torch.float32
+    return k, pairs
+
+
+def resize_pair_u8_batch(raw, descs, size, stride, normalize=True, out=None):
+    """rn_resize_pair_u8_batch: k raw uint8 images in one device buffer, image i in raw[i * stride, (i+1) * stride) with its
+    resize_desc in descs[i] (int32 [k, 4] device tensor) -> [2k, oh, ow, 3] fp32, slots 2i / 2i+1 = resize_pair_u8 of image i,
+    bit for bit, in one launch."""
+    k, pairs = _batch_args(raw, descs, 4, size, stride, out)
+    mean = (C.c_float * 3)(*MEAN) if normalize else None
+    std = (C.c_float * 3)(*STD) if normalize else None
+    _rn.check(_rn.lib().rn_resize_pair_u8_batch(_rn.ptr(raw), int(stride), _rn.ptr(descs), k, _rn.f32(pairs), int(size[0]),
+                                                int(size[1]), mean, std, _rn.stream()), 'rn_resize_pair_u8_batch')
+    return pairs
+
+
+def resize_pair_u8_augment_batch(raw, descs, size, stride, normalize=True, out=None):
+    """rn_resize_pair_u8_augment_batch: resize_pair_u8_batch with the augment_desc of image i in descs[i] (int32 [k, 12] device
+    tensor); slots 2i / 2i+1 = resize_pair_u8_augment of image i, bit for bit.  Two launches whatever k is; every sample's
+    partial channel sums live in the stream's workspace."""
+    k, pairs = _batch_args(raw, descs, 12, size, stride, out)
+    oh, ow = int(size[0]), int(size[1])
+    mean = (C.c_float * 3)(*MEAN) if normalize else None
+    std = (C.c_float * 3)(*STD) if normalize else None
+    L_ = _rn.lib()
+    ws = _rn.workspace(L_.rn_resize_pair_u8_augment_batch_workspace(k, oh, ow), raw.device)
+    _rn.check(L_.rn_resize_pair_u8_augment_batch(_rn.ptr(raw), int(stride), _rn.ptr(descs), k, _rn.f32(pairs), oh, ow, mean, std,
+                                                 ws.data_ptr(), ws.numel(), _rn.stream()), 'rn_resize_pair_u8_augment_batch')
+    return pairs
+
+
 def preprocess_image(image):
     """(image - MEAN) / STD (train.py:48-49) for a float image already at its final size."""
     return rescale_image(image, size=tuple(image.shape[-3:-1]), normalize=True)
@@ -333,15 +374,35 @@ class DeviceFeed(object):
     first_ordinal + i (rank: the loader's), writes the rn_augment_desc and the TRANSFORMED boxes / ids into the pinned slot, and
     `features()` is rn_resize_pair_u8_augment + the paired assignment.  Every parameter reaches the kernels through the uploaded
     descriptor, so the shape key -- and with it the set of captured graphs -- is the same as without a policy.  `last_sample`
-    carries the transformed boxes and the descriptor ('augment_desc').  augment=None / False: the path above, untouched."""
+    carries the transformed boxes and the descriptor ('augment_desc').  augment=None / False: the path above, untouched.
+
+    samples_per_step=K (1 <= K <= 16; ragged mode only; 1 = everything above, untouched): a step trains on a GROUP -- the next
+    sample of the stream plus the samples that follow it while they have the same network input size, K at most (the loader
+    thread looks one sample ahead; the sample it peeked at and did not take opens the next group, and is not staged before
+    that).  Nothing is dropped, reordered or duplicated: the groups, concatenated, are the loader's stream
+    (FileDataset.configure(group=K) orders an epoch so that the groups are full).  The pinned slot and the static device set hold
+    K samples: `raw` K * raw capacity bytes with sample i at i * raw capacity, `desc` [K, 4], `adesc` [K, 12], `boxes`
+    [K, cap, 4], `ids` [K, cap], `nobj` [K]; only the used bytes of every raw image are uploaded.  `features()` of a group of j
+    is rn_resize_pair_u8_batch (or _augment_batch) + ONE paired assignment over j images: `image` [2j, oh, ow, 3], sample i in
+    slots 2i / 2i+1, bit for bit what K = 1 yields for it.  The shape key is (oh, ow, object capacity, generation, j): a partial
+    group is a key -- a graph set -- of its own.  Sample m of the stream is still drawn at ordinal first_ordinal + m, whatever
+    the grouping; `samples_staged` counts samples, `last_sample` is the list of the group's infos."""
+
+    MAX_SAMPLES_PER_STEP = 16
 
     def __init__(self, data_loader, levels, scale=None, device='cuda', max_obj=32, normalize=True, prefetch=3, ragged=False,
-                 decode_workers=4, augment=None, first_ordinal=0):
+                 decode_workers=4, augment=None, first_ordinal=0, samples_per_step=1):
         import queue
         import threading
         self.augment = _policy_or_none(augment)        # (checked before anything touches the device)
         if self.augment is not None and not ragged:
             raise ValueError("DeviceFeed(augment=policy) needs ragged=True: the augmentation kernel reads the raw uint8 image")
+        self.samples_per_step = int(samples_per_step)
+        if not 1 <= self.samples_per_step <= self.MAX_SAMPLES_PER_STEP:
+            raise ValueError("DeviceFeed(samples_per_step=%r): 1 .. %d" % (samples_per_step, self.MAX_SAMPLES_PER_STEP))
+        if self.samples_per_step > 1 and not ragged:
+            raise ValueError("DeviceFeed(samples_per_step=%d) needs ragged=True: the batched preprocess kernels read raw uint8 "
+                             "images" % self.samples_per_step)
         self.levels, self.scale, self.normalize = levels, scale, normalize
         self.num_classes = data_loader.num_classes
         self.device = torch.device(device)
@@ -384,6 +445,8 @@ class DeviceFeed(object):
 
     # -- host side: loader thread
     def _produce(self):
+        if self.ragged and self.samples_per_step > 1:
+            return self._produce_groups()
         if self.ragged:
             return self._produce_ragged()
         try:
@@ -465,6 +528,118 @@ class DeviceFeed(object):
             self._error = e
             self._ready.put(None)
 
+    def _produce_groups(self):
+        """_produce_ragged for samples_per_step > 1: one pinned slot per GROUP of up to K consecutive samples of one network
+        input size (see the class docstring)."""
+        K = self.samples_per_step
+        try:
+            peeked = None                            # the sample looked at to close the previous group: it opens this one
+            while True:
+                group, size = [], None
+                while len(group) < K:
+                    if peeked is None:
+                        peeked = next(self._it, None)
+                        if peeked is None:
+                            break
+                    img = np.asarray(peeked['image'])
+                    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+                        raise ValueError("DeviceFeed(ragged=True) stages uint8 [H, W, 3] images, got %s %s" % (img.dtype, img.shape))
+                    hw = (int(img.shape[0]), int(img.shape[1]))
+                    sz = rescale_size(hw, self.scale) if self.scale is not None else hw
+                    if group and sz != size:
+                        break
+                    group.append(peeked)
+                    size, peeked = sz, None
+                if not group:
+                    break
+                slot = self._free.get()
+                if self._stop:
+                    return
+                if slot is not None and slot[1] is not None:
+                    slot[1].synchronize()
+                images = [np.ascontiguousarray(sample['image']) for sample in group]
+                infos = []
+                for img, sample in zip(images, group):
+                    ids = np.asarray(sample['class_ids'], np.int32).reshape(-1)
+                    h, w = int(img.shape[0]), int(img.shape[1])
+                    boxes = (np.asarray(sample['boxes'], np.float32).reshape(-1, 4) / np.asarray([h, w, h, w], np.float32))   # dataset.py:163
+                    info = {}
+                    if self.augment is not None:
+                        values, boxes, ids = self.augment.draw(self._rank, self._ordinal, (h, w), boxes, ids)
+                        self._ordinal += 1
+                        info['augment_desc'] = augment_desc((h, w), values, size)
+                    infos.append(dict(info, boxes=boxes, class_ids=ids, image_hw=(h, w)))
+                need_raw = max(img.size for img in images)
+                need_obj = max(len(info['class_ids']) for info in infos)
+                if need_raw > self._raw_cap or need_obj > self._obj_cap:          # no hints, or a sample beyond them: grow
+                    self._raw_cap = max(need_raw, -(-self._raw_cap * 3 // 2))
+                    self._obj_cap = max(self._obj_cap, -(-need_obj // 32) * 32)
+                    self._generation += 1
+                host = slot[0] if slot is not None else None
+                if host is None or host['gen'] != self._generation:
+                    host = {'gen': self._generation, 'stride': self._raw_cap,
+                            'raw': torch.empty((K * self._raw_cap,), dtype=torch.uint8).pin_memory(),
+                            'desc': torch.zeros((K, 4), dtype=torch.int32).pin_memory(),
+                            'boxes': torch.zeros((K, self._obj_cap, 4), dtype=torch.float32).pin_memory(),
+                            'ids': torch.zeros((K, self._obj_cap), dtype=torch.int32).pin_memory(),
+                            'nobj': torch.zeros((K,), dtype=torch.int32).pin_memory()}
+                    if self.augment is not None:
+                        host['adesc'] = torch.zeros((K, 12), dtype=torch.int32).pin_memory()
+                host['boxes'].zero_(); host['ids'].zero_(); host['nobj'].zero_()
+                for i, (img, info) in enumerate(zip(images, infos)):
+                    n = len(info['class_ids'])
+                    host['raw'].numpy()[i * host['stride']:i * host['stride'] + img.size] = img.reshape(-1)
+                    host['desc'].numpy()[i] = resize_desc(info['image_hw'], size)
+                    if self.augment is not None:
+                        host['adesc'].numpy()[i] = info['augment_desc']
+                    host['boxes'].numpy()[i, :n] = info['boxes']
+                    host['ids'].numpy()[i, :n] = info['class_ids']
+                    host['nobj'][i] = n
+                host['bytes'], host['size'] = [img.size for img in images], size
+                self._ready.put((host, infos))
+            self._ready.put(None)
+        except BaseException as e:
+            self._error = e
+            self._ready.put(None)
+
+    def _stage_group(self, host, cur):
+        """_stage_ragged for samples_per_step > 1: the first j = len(host['bytes']) samples of the K-sample static set."""
+        j = len(host['bytes'])
+        key = (host['size'][0], host['size'][1], int(host['boxes'].shape[1]), host['gen'], j)
+        if self._static is None or self._static['gen'] != host['gen']:
+            self._static = {k: torch.empty(v.shape, dtype=v.dtype, device=self.device) for k, v in host.items()
+                            if isinstance(v, torch.Tensor)}
+            self._static['gen'], self._static['stride'] = host['gen'], host['stride']
+            self.generations += 1
+        self.shape_key = key
+        self._size, self._group = host['size'], j
+        cs = self._copy_stream
+        if self._consumed is not None:
+            cs.wait_event(self._consumed)
+        else:
+            cs.wait_stream(cur)
+        with torch.cuda.stream(cs):
+            for i, n in enumerate(host['bytes']):
+                lo = i * host['stride']
+                self._static['raw'][lo:lo + n].copy_(host['raw'][lo:lo + n], non_blocking=True)
+            for k in ('desc', 'boxes', 'ids', 'nobj') + (('adesc',) if 'adesc' in host else ()):
+                self._static[k][:j].copy_(host[k][:j], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(cs)
+        cur.wait_event(done)
+        return key, done
+
+    def _features_group(self):
+        s, j = self._static, self._group
+        oh, ow = self._size
+        if self.augment is not None:
+            pairs = resize_pair_u8_augment_batch(s['raw'], s['adesc'][:j], (oh, ow), s['stride'], normalize=self.normalize)
+        else:
+            pairs = resize_pair_u8_batch(s['raw'], s['desc'][:j], (oh, ow), s['stride'], normalize=self.normalize)
+        c, r, m = build_labels((oh, ow), s['ids'][:j], s['boxes'][:j], self.levels, self.num_classes, num_obj=s['nobj'][:j],
+                               flip_pair=True)
+        return {'image': pairs, 'image_size': (oh, ow), 'detection': {'classifications': c, 'regressions': r}, 'trainable_masks': m}
+
     def _stage_ragged(self, host, cur):
         """stage() of the ragged mode: one static set per generation (the previous one is dropped with its generation)."""
         key = (host['size'][0], host['size'][1], int(host['boxes'].shape[1]), host['gen'])
@@ -517,6 +692,12 @@ class DeviceFeed(object):
             raise StopIteration
         host, info = item
         cur = torch.cuda.current_stream(self.device)
+        if self.ragged and self.samples_per_step > 1:
+            key, done = self._stage_group(host, cur)
+            self._free.put((host, done))
+            self.last_sample = info                 # the list of the group's infos
+            self.samples_staged += len(info)
+            return key
         if self.ragged:
             key, done = self._stage_ragged(host, cur)
             self._free.put((host, done))
@@ -551,6 +732,8 @@ class DeviceFeed(object):
 
     def features(self):
         """The step's features from the static buffers (inside the captured segment when the trainer runs graphs)."""
+        if self.ragged and self.samples_per_step > 1:
+            return self._features_group()
         if self.ragged:
             return self._features_ragged()
         s = self._static

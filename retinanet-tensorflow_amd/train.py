@@ -941,6 +941,9 @@ def build_parser():
     parser.add_argument('--augment-crop', type=float, default=None, metavar='S',
                         help='with --augment: also a random crop of side fraction U[S, 1] (0 < S <= 1), boxes clipped to it')
     parser.add_argument('--augment-seed', type=int, default=None, metavar='N', help='with --augment: seed of the draws (default 0)')
+    parser.add_argument('--samples-per-step', type=int, default=1, metavar='K',
+                        help='file datasets: train on up to K samples of one network input size per step (a batch of 2K images: '
+                             'every sample and its h-flip; 1 <= K <= 16, default 1)')
     parser.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of replaying the captured step')
     return parser
 
@@ -1000,18 +1003,33 @@ def main(argv=None):
         parser.error('--augment-crop / --augment-seed need --augment')
     if args.augment_crop is not None and not (0.0 < args.augment_crop <= 1.0):
         parser.error('--augment-crop S: 0 < S <= 1 (got %g)' % args.augment_crop)
+    K = args.samples_per_step
+    if K != 1 and not files:
+        parser.error('--samples-per-step groups raw uint8 image files: it needs --dataset pascal ... or coco ...')
+    if not 1 <= K <= 16:
+        parser.error('--samples-per-step K: 1 <= K <= 16 (got %d)' % K)
     dev, rank, world, started = init_distributed()
     from data_loaders.shapes import Shapes
     # every replica draws its own samples (dataset.py:182-204: a replica's batch is [sample, hflip(sample)])
     if files:
         from data_loaders.inferred import Inferred
         # one epoch = a permutation seeded by (0, epoch), sample i to rank i % world, runs of one network input size
+        # (--samples-per-step K > 1: full groups of K samples of one size instead of the runs, data_loaders/files.py)
         loader = Inferred(kind, dargs).configure(seed=0, rank=rank, world=world, scale=args.scale, repeat=True,
-                                                 shape_runs=8 if args.shape_runs is None else args.shape_runs)
-        steps_per_epoch = args.steps_per_epoch or max(1, len(loader.records) // world)    # every rank runs the same steps
+                                                 shape_runs=8 if args.shape_runs is None else args.shape_runs,
+                                                 **({'group': K} if K > 1 else {}))
+        if K > 1:
+            # a step is a group, and ranks form different numbers of groups from their shards: every rank computes every rank's
+            # count for epoch 0 (no I/O) and all run the smallest -- unequal step counts would leave a rank waiting in a collective
+            steps_per_epoch = args.steps_per_epoch or max(1, min(loader.epoch_steps(0, r) for r in range(world)))
+        else:
+            steps_per_epoch = args.steps_per_epoch or max(1, len(loader.records) // world)    # every rank runs the same steps
         if rank == 0:
             print('%s: %d images (%d skipped: no valid box), %d steps per epoch' % (kind, len(loader.records), loader.skipped,
                                                                                   steps_per_epoch), flush=True)
+            if K > 1:
+                print('%d images per step: %d samples of one input size and their h-flips (fewer where a group is partial)'
+                      % (2 * K, K), flush=True)
     elif dargs:
         loader = Shapes(dargs[0], image_size=(int(dargs[2]), int(dargs[2])), seed=rank)
         steps_per_epoch = args.steps_per_epoch or int(dargs[1])
@@ -1035,13 +1053,15 @@ def main(argv=None):
     # (first_ordinal = samples_drawn holds because every staged sample is one sample of the loader's stream: the file readers drop
     # invalid records once, up front, so Inferred skips nothing while iterating -- checked where the checkpoint is written)
     skipped0 = getattr(loader, 'skipped', 0)
+    group_kw = {'samples_per_step': K} if K > 1 else {}
     if files and args.augment:
         import augmentation
         policy = augmentation.Policy(crop_min=1.0 if args.augment_crop is None else args.augment_crop, seed=args.augment_seed or 0)
         feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev, ragged=True, decode_workers=args.decode_workers,
-                                  augment=policy, first_ordinal=drawn0)
+                                  augment=policy, first_ordinal=drawn0, **group_kw)
     elif files:
-        feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev, ragged=True, decode_workers=args.decode_workers)
+        feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev, ragged=True, decode_workers=args.decode_workers,
+                                  **group_kw)
     else:
         feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev)
     trainer = Trainer(net, levels, optimizer=args.optimizer, learning_rate=args.learning_rate,

@@ -4,9 +4,12 @@ images/s (two per step: [image, hflip]), recaptures per 100 steps, the host deco
 shapes stream at the same --scale.  The training times are wall time of train.main's loop, graph captures included.
 
     python tools/files_bench.py DIR [--images 96] [--steps 200] [--scale 512] [--decode-workers 4] [--shape-runs 0 8] [--augment [S]]
+                                [--samples-per-step K]
 
 --augment [S]: the file runs train with --augment (and --augment-crop S when S is given): the cost of the augmentation kernels and of
 the loader thread's draws shows as the difference to a run without it.
+--samples-per-step K: the file runs train with --samples-per-step K (K > 1: 2K images per step, the loader orders by groups and
+--shape-runs only labels the line); images/s counts the staged samples, so lines of different K compare directly.
 """
 import argparse
 import json
@@ -51,6 +54,7 @@ def main():
     ap.add_argument('--backbone', default='mobilenet_v2')
     ap.add_argument('--shape-runs', type=int, nargs='+', default=[0, 8])
     ap.add_argument('--augment', type=float, nargs='?', const=1.0, default=None, metavar='S')
+    ap.add_argument('--samples-per-step', type=int, default=1, metavar='K')
     ap.add_argument('--no-shapes', action='store_true', help='skip the in-memory shapes stream')
     a = ap.parse_args()
     import dataset
@@ -66,9 +70,11 @@ def main():
     aug = []
     if a.augment is not None:
         aug = ['--augment'] + (['--augment-crop', str(a.augment)] if a.augment < 1.0 else [])
+    group = ['--samples-per-step', str(a.samples_per_step)] if a.samples_per_step != 1 else []
     for k in a.shape_runs:
-        r = run(['--dataset', 'pascal', a.dir, 'trainval', '--shape-runs', str(k), '--decode-workers', str(a.decode_workers)] + common + aug)
-        print(json.dumps(dict(what='pascal', shape_runs=k, augment=a.augment, **r)), flush=True)
+        r = run(['--dataset', 'pascal', a.dir, 'trainval', '--shape-runs', str(k), '--decode-workers', str(a.decode_workers)] + common + aug
+                + group)
+        print(json.dumps(dict(what='pascal', shape_runs=k, augment=a.augment, samples_per_step=a.samples_per_step, **r)), flush=True)
     if not a.no_shapes:
         r = run(['--dataset', 'shapes'] + common)
         print(json.dumps(dict(what='shapes', **r)), flush=True)
