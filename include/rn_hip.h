@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 410
+#define RN_API_VERSION 411
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -904,6 +904,36 @@ int rn_optimizer_step_norm(int kind, float* w, const float* grad, float* state1,
                            int64_t count, float lr, float grad_scale, int64_t step, uint64_t* advance_counter,
                            uint64_t advance_by, double* partial, rn_stream_t stream);
 int rn_norm_reg_finalize(const double* partial, int64_t npairs, float* out2, rn_stream_t stream);
+
+/* Learning-rate schedules evaluated ON THE DEVICE (the reference trains at one constant rate, train.py:114-119; its TODO list:
+ * "try other scheduling schemes").  A rate that is a launch argument is a constant of a captured step: a schedule would capture
+ * the step again for every rate.  Here the rate is a function of a device step word, so a replayed hipGraph advances it itself.
+ * With s = updates already applied, W = warmup_steps, f0 = warmup_factor, T = total_steps, ff = final_factor:
+ *   s <  W                 lr = base_lr * (f0 + (1 - f0) * s / W)
+ *   s >= W  RN_LR_CONSTANT lr = base_lr
+ *           RN_LR_STEP     lr = base_lr * decay_factor ^ #{i : boundaries[i] <= s}
+ *           RN_LR_COSINE   lr = base_lr * (ff + (1 - ff) * 0.5 * (1 + cos(pi * min(1, (s - W) / (T - W)))))
+ * all in double, rounded to float once.  Checked by the entry: kind; warmup_steps >= 0; f0, ff in [0, 1]; n_boundaries in
+ * [0, RN_LR_MAX_BOUNDARIES], boundaries >= 0 and strictly increasing; total_steps > warmup_steps (RN_LR_COSINE needs it; the
+ * other kinds do not read it and also take 0 = unset). */
+enum rn_lr_kind { RN_LR_CONSTANT = 0, RN_LR_STEP = 1, RN_LR_COSINE = 2 };
+#define RN_LR_MAX_BOUNDARIES 8
+typedef struct rn_lr_schedule {
+  int32_t kind;
+  int32_t n_boundaries;
+  double base_lr, warmup_factor, final_factor, decay_factor;
+  int64_t warmup_steps, total_steps;
+  int64_t boundaries[RN_LR_MAX_BOUNDARIES];
+} rn_lr_schedule;
+/* One thread: s = *step_dev;  lr_dev[0] = lr(s);  lr_dev[1] = the rate the update kernel multiplies by -- for RN_OPT_ADAM
+ * lr(s) * sqrt(1 - 0.999^t) / (1 - 0.9^t), t = s + 1, formed in double from the rounded lr(s) exactly as rn_optimizer_step forms
+ * it from its float argument; lr(s) itself for the other kinds;  *step_dev = s + 1.  No argument changes from step to step. */
+int rn_lr_schedule_eval(rn_lr_schedule sched, uint64_t* step_dev, float* lr_dev, int optimizer_kind, rn_stream_t stream);
+/* rn_optimizer_step_norm with the rate read from lr_dev[1] (what rn_lr_schedule_eval left there; a launch on another stream must
+ * be ordered behind it) instead of a float argument, and hence no `step`: same kernel, same grid, same `partial` layout. */
+int rn_optimizer_step_norm_lrdev(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
+                                 int64_t count, const float* lr_dev, float grad_scale, uint64_t* advance_counter,
+                                 uint64_t advance_by, double* partial, rn_stream_t stream);
 /* *counter += inc on the stream (the same counter, for callers that run backward passes without an optimizer step) */
 int rn_counter_add(uint64_t* counter, uint64_t inc, rn_stream_t stream);
 /* p[0..count) = 0 (16-byte aligned): the gradient arena before a backward pass (the reference's graph zero-initialises

@@ -18,12 +18,20 @@ ACT = {None: 0, "none": 0, "linear": 0, "relu": 1, "elu": 2, "relu6": 3, "sigmoi
 LOSS_MODE = {"bce_dice": 0, "focal": 1}
 OPT = {"momentum": 0, "rmsprop": 1, "adam": 2}
 OPT_BLOCK = 1024
+LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
-API_VERSION = 410        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 411        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
     pass
+
+
+class LrSchedule(C.Structure):
+    """rn_lr_schedule (passed by value); built by train.LRSchedule.struct()."""
+    _fields_ = [("kind", C.c_int32), ("n_boundaries", C.c_int32), ("base_lr", C.c_double), ("warmup_factor", C.c_double),
+                ("final_factor", C.c_double), ("decay_factor", C.c_double), ("warmup_steps", C.c_int64), ("total_steps", C.c_int64),
+                ("boundaries", C.c_int64 * LR_MAX_BOUNDARIES)]
 
 
 class ConvSeg(C.Structure):
@@ -192,6 +200,7 @@ SYMBOLS = [
     "rn_mb_pointwise_bwd_rows", "rn_mb_pointwise_bwd_workspace", "rn_mb_pointwise_bwd",
     "rn_mb_depthwise_bwd_rows", "rn_mb_depthwise_bwd_workspace", "rn_mb_depthwise_bwd",
     "rn_debug_collective_standin", "rn_optimizer_norm_pairs", "rn_optimizer_step_norm", "rn_norm_reg_finalize",
+    "rn_lr_schedule_eval", "rn_optimizer_step_norm_lrdev",
 ]
 
 
@@ -233,6 +242,9 @@ def lib():
         L.rn_optimizer_step_norm.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_uint64,
                                              C.c_void_p, C.c_void_p]
         L.rn_norm_reg_finalize.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.rn_lr_schedule_eval.argtypes = [LrSchedule, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.rn_optimizer_step_norm_lrdev.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_uint64,
+                                                   C.c_void_p, C.c_void_p]
         L.rn_debug_collective_standin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p]
         L.rn_conv2d_stats_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.rn_conv2d_fwd_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -39,6 +39,12 @@ def load_extra(path):
     return json.loads(meta["extra"]) if "extra" in meta else {}
 
 
+def saved_step(path):
+    """The step a checkpoint was saved at (what load() returns), without reading a tensor."""
+    with safe_open(path, framework="pt") as f:
+        return int((f.metadata() or {}).get("step", 0))
+
+
 def load(path, net, trainer=None):
     """Restores in place (the parameters keep pointing into the trainer's arena).  Returns the saved step.
     Missing keys and shape mismatches raise a ValueError that names the parameter."""
@@ -86,7 +92,8 @@ def load(path, net, trainer=None):
                 if "trainer/drop_counter" in keys:
                     trainer.drop_counter.copy_((f.get_tensor("trainer/drop_counter") + int(getattr(trainer, "drop_rank_offset", 0)))
                                                .to(trainer.drop_counter.device))
-                trainer.opt.step_count = int(meta.get("step_count", 0))
+                # (also the device step word of a learning-rate schedule: a resumed run continues the schedule where it stopped)
+                trainer.opt.set_step_count(int(meta.get("step_count", 0)))
     import ops_f16
     ops_f16.weights_changed()
     return int(meta.get("step", 0))

@@ -49,9 +49,10 @@ __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, cons
                                                      float* __restrict__ s1, float* __restrict__ s2,
                                                      const float* __restrict__ wd, int64_t count, float lr, float gs,
                                                      float clip, const float* __restrict__ norm_sq, unsigned long long* advance, unsigned long long advance_by,
-                                                     double* __restrict__ partial) {
+                                                     double* __restrict__ partial, const float* __restrict__ lr_dev) {
   __shared__ double red[2][T / 64];
   double n2 = 0.0, rg = 0.0;
+  if (lr_dev) lr = lr_dev[1];  // the rate rn_lr_schedule_eval left on the device: one uniform load per wave, ahead of the loop
   if (advance && blockIdx.x == 0 && threadIdx.x == 0) *advance += advance_by;  // the step counter the dropout masks hash (fresh masks next step)
   float cs = 1.f;
   if (clip > 0.f) {
@@ -132,9 +133,10 @@ extern "C" int rn_grad_norm_l2reg(const float* w, const float* grad, const float
 }
 
 namespace {
+// lr_dev (optional): the kernel reads its rate from lr_dev[1] -- bias correction included -- and `lr` / `step` are not used
 int launch_opt(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block, int64_t count, float lr,
                float grad_scale, float clip_norm, const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
-               double* partial, hipStream_t st) {
+               double* partial, hipStream_t st, const float* lr_dev = nullptr) {
   RN_CHECK_ARG(w && grad && state1 && wd_per_block, "optimizer: null pointer");
   RN_CHECK_ARG(count > 0 && count % RN_OPT_BLOCK == 0, "optimizer: count %lld not a multiple of %d", (long long)count,
                RN_OPT_BLOCK);
@@ -142,19 +144,19 @@ int launch_opt(int kind, float* w, const float* grad, float* state1, float* stat
   RN_CHECK_ARG(kind == RN_OPT_MOMENTUM || state2, "optimizer: state2 required for rmsprop/adam");
   const unsigned nb = grid_for(count / 4);
   float lr_eff = lr;
-  if (kind == RN_OPT_ADAM) {
+  if (kind == RN_OPT_ADAM && !lr_dev) {
     RN_CHECK_ARG(step >= 1, "optimizer: adam step must be >= 1");
     lr_eff = (float)((double)lr * sqrt(1.0 - pow(0.999, (double)step)) / (1.0 - pow(0.9, (double)step)));
-  } else if (kind != RN_OPT_MOMENTUM && kind != RN_OPT_RMSPROP) {
+  } else if (kind != RN_OPT_MOMENTUM && kind != RN_OPT_RMSPROP && kind != RN_OPT_ADAM) {
     rn::set_error("optimizer: unknown kind %d", kind);
     return RN_EINVAL;
   }
 #define RN_OPT_LAUNCH(KIND_)                                                                                                  \
   do {                                                                                                                        \
     if (partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true>), dim3(nb), dim3(T), 0, st, w, grad, state1, state2, wd_per_block, count, lr_eff, \
-                                    grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter, (unsigned long long)advance_by, partial); \
+                                    grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter, (unsigned long long)advance_by, partial, lr_dev); \
     else hipLaunchKernelGGL((opt_step_kernel<KIND_, false>), dim3(nb), dim3(T), 0, st, w, grad, state1, state2, wd_per_block, count, lr_eff, \
-                            grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter, (unsigned long long)advance_by, partial); \
+                            grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter, (unsigned long long)advance_by, partial, lr_dev); \
   } while (0)
   if (kind == RN_OPT_MOMENTUM) RN_OPT_LAUNCH(RN_OPT_MOMENTUM);
   else if (kind == RN_OPT_RMSPROP) RN_OPT_LAUNCH(RN_OPT_RMSPROP);
@@ -180,6 +182,67 @@ extern "C" int rn_optimizer_step_norm(int kind, float* w, const float* grad, flo
   RN_CHECK_ARG(partial, "optimizer step + norm: null partial buffer");
   return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, 0.f, nullptr, step, advance_counter, advance_by,
                     partial, (hipStream_t)stream);
+}
+
+extern "C" int rn_optimizer_step_norm_lrdev(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
+                                            int64_t count, const float* lr_dev, float grad_scale, uint64_t* advance_counter,
+                                            uint64_t advance_by, double* partial, rn_stream_t stream) {
+  RN_CHECK_ARG(partial, "optimizer step + norm: null partial buffer");
+  RN_CHECK_ARG(lr_dev, "optimizer step + norm: null device rate");
+  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, 0.f, grad_scale, 0.f, nullptr, 0, advance_counter, advance_by,
+                    partial, (hipStream_t)stream, lr_dev);
+}
+
+namespace {
+// lr(s) of rn_lr_schedule (include/rn_hip.h), in double; the caller rounds it to float once
+__device__ double lr_schedule_value(const rn_lr_schedule& d, uint64_t s) {
+  const double base = d.base_lr;
+  if (s < (uint64_t)d.warmup_steps) return base * (d.warmup_factor + (1.0 - d.warmup_factor) * (double)s / (double)d.warmup_steps);
+  if (d.kind == RN_LR_STEP) {
+    int passed = 0;
+    for (int i = 0; i < d.n_boundaries; ++i) passed += ((uint64_t)d.boundaries[i] <= s) ? 1 : 0;
+    return base * pow(d.decay_factor, (double)passed);
+  }
+  if (d.kind == RN_LR_COSINE) {
+    const double span = (double)(d.total_steps - d.warmup_steps);
+    const double frac = fmin(1.0, (double)(s - (uint64_t)d.warmup_steps) / span);
+    return base * (d.final_factor + (1.0 - d.final_factor) * 0.5 * (1.0 + cos(3.14159265358979323846 * frac)));
+  }
+  return base;
+}
+
+__global__ void lr_schedule_eval_kernel(rn_lr_schedule d, unsigned long long* step_dev, float* lr_dev, int opt_kind) {
+  const unsigned long long s = *step_dev;
+  const float lr = (float)lr_schedule_value(d, (uint64_t)s);
+  float eff = lr;
+  if (opt_kind == RN_OPT_ADAM) {
+    const double t = (double)(s + 1);
+    eff = (float)((double)lr * sqrt(1.0 - pow(0.999, t)) / (1.0 - pow(0.9, t)));
+  }
+  lr_dev[0] = lr;
+  lr_dev[1] = eff;
+  *step_dev = s + 1;
+}
+}  // namespace
+
+extern "C" int rn_lr_schedule_eval(rn_lr_schedule d, uint64_t* step_dev, float* lr_dev, int optimizer_kind, rn_stream_t stream) {
+  RN_CHECK_ARG(step_dev && lr_dev, "lr_schedule_eval: null pointer");
+  RN_CHECK_ARG(optimizer_kind == RN_OPT_MOMENTUM || optimizer_kind == RN_OPT_RMSPROP || optimizer_kind == RN_OPT_ADAM,
+               "lr_schedule_eval: unknown optimizer kind %d", optimizer_kind);
+  RN_CHECK_ARG(d.kind == RN_LR_CONSTANT || d.kind == RN_LR_STEP || d.kind == RN_LR_COSINE, "lr_schedule_eval: unknown kind %d", d.kind);
+  RN_CHECK_ARG(d.warmup_steps >= 0, "lr_schedule_eval: warmup_steps %lld < 0", (long long)d.warmup_steps);
+  RN_CHECK_ARG(d.warmup_factor >= 0.0 && d.warmup_factor <= 1.0 && d.final_factor >= 0.0 && d.final_factor <= 1.0,
+               "lr_schedule_eval: warmup_factor %g / final_factor %g outside [0, 1]", d.warmup_factor, d.final_factor);
+  RN_CHECK_ARG(d.n_boundaries >= 0 && d.n_boundaries <= RN_LR_MAX_BOUNDARIES, "lr_schedule_eval: %d boundaries, at most %d",
+               d.n_boundaries, RN_LR_MAX_BOUNDARIES);
+  for (int i = 0; i < d.n_boundaries; ++i)
+    RN_CHECK_ARG(d.boundaries[i] >= 0 && (i == 0 || d.boundaries[i] > d.boundaries[i - 1]),
+                 "lr_schedule_eval: boundaries must be non-negative and strictly increasing (entry %d)", i);
+  RN_CHECK_ARG(d.total_steps > d.warmup_steps || (d.kind != RN_LR_COSINE && d.total_steps == 0),
+               "lr_schedule_eval: total_steps %lld is not above warmup_steps %lld", (long long)d.total_steps, (long long)d.warmup_steps);
+  hipLaunchKernelGGL(lr_schedule_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d, (unsigned long long*)step_dev, lr_dev, optimizer_kind);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
 }
 
 extern "C" int rn_norm_reg_finalize(const double* partial, int64_t npairs, float* out2, rn_stream_t stream) {

@@ -17,6 +17,7 @@ hipGraph -- the launch-bound small kernels of the pyramid's coarse levels then c
 import collections
 import contextlib
 import ctypes
+import math
 import os
 import sys
 import time
@@ -72,15 +73,115 @@ class ParamArena(object):
             self.grads.zero_()
 
 
+class LRSchedule(object):
+    """The learning rate as a function of s, the number of updates already applied (the reference trains at one constant rate;
+    its TODO list: "try other scheduling schemes").  W = warmup_steps, f0 = warmup_factor, T = total_steps, ff = final_factor:
+
+        s <  W             base * (f0 + (1 - f0) * s / W)
+        s >= W  constant   base
+                step       base * decay_factor ** #{boundaries b <= s}
+                cosine     base * (ff + (1 - ff) * 0.5 * (1 + cos(pi * min(1, (s - W) / (T - W)))))
+
+    in float64, rounded to float32 once.  rn_lr_schedule_eval evaluates the same descriptor on the device (struct()), where a
+    replayed graph advances it by itself; value(s) is the host's copy of the formula (launch arguments of the clipping path,
+    logging, tests).  Immutable and hashable: it is part of the one-graph step's cache key."""
+
+    KINDS = ('constant', 'step', 'cosine')
+    MAX_BOUNDARIES = _rn.LR_MAX_BOUNDARIES
+
+    def __init__(self, kind='constant', base_lr=1e-2, warmup_steps=0, warmup_factor=1.0 / 3.0, boundaries=(), decay_factor=0.1,
+                 total_steps=None, final_factor=0.0):
+        if kind not in self.KINDS:
+            raise ValueError("lr schedule: kind %r is none of %s" % (kind, ', '.join(self.KINDS)))
+        boundaries = tuple(int(b) for b in boundaries)
+        warmup_steps = int(warmup_steps)
+        total_steps = None if total_steps is None else int(total_steps)
+        if warmup_steps < 0:
+            raise ValueError("lr schedule: warmup_steps %d < 0" % warmup_steps)
+        if not (0.0 <= warmup_factor <= 1.0 and 0.0 <= final_factor <= 1.0):
+            raise ValueError("lr schedule: warmup_factor %g and final_factor %g must lie in [0, 1]" % (warmup_factor, final_factor))
+        if len(boundaries) > self.MAX_BOUNDARIES:
+            raise ValueError("lr schedule: %d boundaries, at most %d" % (len(boundaries), self.MAX_BOUNDARIES))
+        if any(b < 0 for b in boundaries) or any(b <= a for a, b in zip(boundaries, boundaries[1:])):
+            raise ValueError("lr schedule: boundaries %s are not non-negative and strictly increasing" % (boundaries,))
+        if boundaries and kind != 'step':
+            raise ValueError("lr schedule: boundaries belong to kind 'step' (got %r)" % kind)
+        if kind == 'cosine' and total_steps is None:
+            raise ValueError("lr schedule: kind 'cosine' needs total_steps")
+        if total_steps is not None and total_steps <= warmup_steps:
+            raise ValueError("lr schedule: total_steps %d is not above warmup_steps %d" % (total_steps, warmup_steps))
+        self._key = (kind, float(base_lr), warmup_steps, float(warmup_factor), boundaries, float(decay_factor), total_steps,
+                     float(final_factor))
+
+    kind = property(lambda self: self._key[0])
+    base_lr = property(lambda self: self._key[1])
+    warmup_steps = property(lambda self: self._key[2])
+    warmup_factor = property(lambda self: self._key[3])
+    boundaries = property(lambda self: self._key[4])
+    decay_factor = property(lambda self: self._key[5])
+    total_steps = property(lambda self: self._key[6])
+    final_factor = property(lambda self: self._key[7])
+
+    def __hash__(self):
+        return hash(self._key)
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self._key == other._key
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __repr__(self):
+        return "LRSchedule(kind=%r, base_lr=%r, warmup_steps=%r, warmup_factor=%r, boundaries=%r, decay_factor=%r, " \
+               "total_steps=%r, final_factor=%r)" % self._key
+
+    def value(self, s):
+        kind, base, W, f0, bounds, decay, T, ff = self._key
+        s = int(s)
+        if s < W:
+            lr = base * (f0 + (1.0 - f0) * s / W)
+        elif kind == 'step':
+            lr = base * decay ** sum(1 for b in bounds if b <= s)
+        elif kind == 'cosine':
+            lr = base * (ff + (1.0 - ff) * 0.5 * (1.0 + math.cos(math.pi * min(1.0, (s - W) / float(T - W)))))
+        else:
+            lr = base
+        return np.float32(lr)
+
+    def struct(self):
+        """The descriptor rn_lr_schedule_eval takes by value (rn_lr_schedule of include/rn_hip.h)."""
+        kind, base, W, f0, bounds, decay, T, ff = self._key
+        d = _rn.LrSchedule(kind=self.KINDS.index(kind), n_boundaries=len(bounds), base_lr=base, warmup_factor=f0,
+                           final_factor=ff, decay_factor=decay, warmup_steps=W, total_steps=T or 0)
+        for i, b in enumerate(bounds):
+            d.boundaries[i] = b
+        return d
+
+
 class Optimizer(object):
     """tf.train.MomentumOptimizer(lr, 0.9) | RMSPropOptimizer(lr, 0.9, 0.9) | AdamOptimizer(lr)
-    (train.py:114-119) + optional tf.clip_by_global_norm (train.py:127-132), one fused kernel."""
+    (train.py:114-119) + optional tf.clip_by_global_norm (train.py:127-132), one fused kernel.
 
-    def __init__(self, arena, kind='momentum', learning_rate=1e-2, grad_clip_norm=None):
+    `schedule` (LRSchedule): the rate of update s is schedule.value(s); `lr` stays the base rate.  On a device arena without
+    clipping the rate never passes through the host: begin_step launches rn_lr_schedule_eval, which reads the device step word
+    `step_dev`, leaves [lr(s), the rate the update multiplies by] in `lr_dev` and advances the word; the slices' update kernels read
+    lr_dev[1].  No launch argument of such a step changes from one step to the next, Adam's bias correction included."""
+
+    def __init__(self, arena, kind='momentum', learning_rate=1e-2, grad_clip_norm=None, schedule=None):
         assert kind in ['momentum', 'adam', 'rmsprop']
         self.arena, self.kind, self.lr = arena, kind, float(learning_rate)
         self.clip = float(grad_clip_norm) if grad_clip_norm is not None else 0.0
         dev = arena.weights.device
+        self.schedule = schedule
+        if schedule is not None:
+            assert isinstance(schedule, LRSchedule)
+            self.lr = schedule.base_lr
+        # allocated HERE like _partial below (a lazy zero-fill inside a step would not be ordered against a side stream's slice)
+        self.step_dev = self.lr_dev = self._sched_struct = self._sched_event = None
+        if schedule is not None and dev.type == 'cuda':
+            self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)        # (the kernel's uint64: same bits)
+            self.lr_dev = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._sched_struct = schedule.struct()
         self.state1 = torch.ones_like(arena.weights) if kind == 'rmsprop' else torch.zeros_like(arena.weights)
         self.state2 = torch.zeros_like(arena.weights) if kind != 'momentum' else None
         self.norm_reg = torch.zeros(2, dtype=torch.float32, device=dev)   # [sum g'^2, L2 reg loss]
@@ -107,10 +208,11 @@ class Optimizer(object):
         _rn.check(L_.rn_grad_norm_l2reg(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count,
                                         grad_scale, _rn.f32(self.norm_reg), ws.data_ptr(), ws.numel(), _rn.stream()),
                   'rn_grad_norm_l2reg')
+        lr = self.current_lr()           # (the rate is a launch argument of this path: a schedule is evaluated on the host)
         self.step_count += 1
         _rn.check(L_.rn_optimizer_step(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
                                        _rn.f32(self.state2) if self.state2 is not None else None,
-                                       _rn.f32(a.wd_per_block), a.count, self.lr, grad_scale, self.clip,
+                                       _rn.f32(a.wd_per_block), a.count, lr, grad_scale, self.clip,
                                        _rn.f32(self.norm_reg), self.step_count,
                                        advance_counter.data_ptr() if advance_counter is not None else None,
                                        ops.DROPOUT_COUNTER_STEP, _rn.stream()), 'rn_optimizer_step')
@@ -123,6 +225,12 @@ class Optimizer(object):
         self.step_count += 1
         self._pairs = 0
         assert self._partial is not None, "the fused norm path needs a device arena"
+        if self.lr_dev is not None:
+            # this update's rate, on the main stream ahead of every slice; the kernel advances step_dev itself
+            _rn.check(_rn.lib().rn_lr_schedule_eval(self._sched_struct, self.step_dev.data_ptr(), _rn.f32(self.lr_dev),
+                                                    _rn.OPT[self.kind], _rn.stream()), 'rn_lr_schedule_eval')
+            self._sched_event = torch.cuda.Event()
+            self._sched_event.record()
 
     def step_slice(self, lo, hi, grad_scale, advance_counter=None, stream=None):
         a, L_ = self.arena, _rn.lib()
@@ -131,6 +239,19 @@ class Optimizer(object):
         assert 2 * (self._pairs + npairs) <= self._partial.numel()
         part = self._partial[2 * self._pairs:]
         self._pairs += npairs
+        if self.lr_dev is not None:
+            if stream is not None:       # a slice on another stream reads lr_dev too: behind the schedule kernel, not the whole main stream
+                other = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(getattr(stream, 'value', stream)))
+                other.wait_event(self._sched_event)
+                stream = ctypes.c_void_p(other.cuda_stream)
+            _rn.check(L_.rn_optimizer_step_norm_lrdev(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(),
+                                                      self.state1[lo:].data_ptr(),
+                                                      self.state2[lo:].data_ptr() if self.state2 is not None else None,
+                                                      a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), hi - lo, _rn.f32(self.lr_dev), grad_scale,
+                                                      advance_counter.data_ptr() if advance_counter is not None else None,
+                                                      ops.DROPOUT_COUNTER_STEP, part.data_ptr(),
+                                                      stream if stream is not None else _rn.stream()), 'rn_optimizer_step_norm_lrdev')
+            return
         _rn.check(L_.rn_optimizer_step_norm(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(), self.state1[lo:].data_ptr(),
                                             self.state2[lo:].data_ptr() if self.state2 is not None else None,
                                             a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), hi - lo, self.lr, grad_scale, self.step_count,
@@ -142,6 +263,16 @@ class Optimizer(object):
                   'rn_norm_reg_finalize')
         import ops_f16
         ops_f16.weights_changed()
+
+    def current_lr(self):
+        """The rate of the NEXT update, from the host's step count (no device synchronisation)."""
+        return self.lr if self.schedule is None else float(self.schedule.value(self.step_count))
+
+    def set_step_count(self, n):
+        """Updates applied so far (a restored checkpoint): the host's count and the device word the schedule kernel reads."""
+        self.step_count = int(n)
+        if self.step_dev is not None:
+            self.step_dev.fill_(self.step_count)
 
     @property
     def regularization_loss(self):
@@ -271,7 +402,7 @@ class Trainer(object):
     def __init__(self, net, levels=None, optimizer='momentum', learning_rate=1e-2, grad_clip_norm=None,
                  loss_mode='bce_dice', device='cuda', use_graph=False, process_group=None,
                  direct_param_grads=True, wgrad_side_stream=False, defer_reductions=True, overlap=True,
-                 force_collective=False, input_fn=None, check_interval=50, capture_collectives=None):
+                 force_collective=False, input_fn=None, check_interval=50, capture_collectives=None, lr_schedule=None):
         self.net, self.levels = net, levels or build_levels()
         self.device = torch.device(device)
         if self.device.type == 'cuda':
@@ -284,7 +415,9 @@ class Trainer(object):
         # bias-corrected learning rate is a fresh launch argument every step, also with use_graph=True)
         self.loss_mode = loss_mode
         self.arena = ParamArena(net, self.device)
-        self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm)
+        # lr_schedule (LRSchedule): the rate lives on the device and advances inside the step (Optimizer docstring); None: the
+        # constant `learning_rate`, a launch argument
+        self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule)
         self.allreduce = GradientAllReduce(self.arena, process_group, force=force_collective)
         self.use_graph = use_graph
         self.input_fn = input_fn       # optional: features = input_fn(), run INSIDE segment A (e.g. device-side label assignment)
@@ -363,7 +496,9 @@ class Trainer(object):
         # nothing has to happen on the host between its parts: the ~80 us a step the GPU idles at the graph boundaries and in
         # front of an eagerly launched update (profiles/r05_bench_step_timeline.txt: "idle stretches") disappear.  The update's
         # host-side scalars are constants of such a graph: momentum SGD without clipping only (no step-dependent scalar), and a
-        # changed learning rate captures again (the rate is part of the cache key).  RN_WHOLE_STEP_GRAPH=0: one graph per part.
+        # changed learning rate captures again (the rate is part of the cache key).  With an lr_schedule the update has no such
+        # scalar -- rate and Adam's bias correction are read from the device -- so RMSProp and Adam qualify too and the schedule,
+        # not a rate, is part of the key.  RN_WHOLE_STEP_GRAPH=0: one graph per part.
         self.schedule = []             # the gradient slices of the last recorded / eager step, in the order their all-reduce was issued
         self._last_lr, self._lr_changes = None, 0
         self.recaptures = 0
@@ -700,7 +835,7 @@ class Trainer(object):
         ar = self.allreduce
         return (self.whole_step_graph and self.use_graph and self.device.type == 'cuda'
                 and (not ar.active or (getattr(ar, 'capturable', False) and not getattr(ar, 'host_staged', False)))
-                and self.opt.kind == 'momentum' and self.opt.clip <= 0.0 and FUSED_OPT_NORM)
+                and (self.opt.kind == 'momentum' or self.opt.lr_dev is not None) and self.opt.clip <= 0.0 and FUSED_OPT_NORM)
 
     def _capture_whole(self, features):
         """_run_step as ONE graph (see __init__: whole_step_graph): with several ranks the collectives are nodes of it."""
@@ -722,7 +857,8 @@ class Trainer(object):
         feed = self.input_fn if (features is None and hasattr(self.input_fn, 'stage')) else None
         key = feed.stage() if feed is not None else None
         whole = self._whole_step_ok()
-        if whole:
+        scheduled = self.opt.lr_dev is not None       # the rate is read from the device: no constant of the graph changes
+        if whole and not scheduled:
             # the one-graph step bakes the learning rate into the captured update: a rate that keeps changing (a schedule, a warm-up)
             # would capture again every step -- two warm-up passes + a capture each time, churning the graph cache.  After the third
             # distinct rate the trainer keeps to one graph per part with the update launched eagerly (its scalars are launch arguments).
@@ -734,7 +870,7 @@ class Trainer(object):
             if self._lr_changes > 3:
                 whole = False
         if whole:
-            key = (key, 'whole', self.opt.lr, id(self.allreduce))
+            key = (key, 'whole', self.opt.schedule if scheduled else self.opt.lr, id(self.allreduce))
         if self.use_graph:
             if self._graphs is None:
                 self._graph_cache.clear()
@@ -945,7 +1081,62 @@ def build_parser():
                         help='file datasets: train on up to K samples of one network input size per step (a batch of 2K images: '
                              'every sample and its h-flip; 1 <= K <= 16, default 1)')
     parser.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of replaying the captured step')
+    # learning-rate schedule (LRSchedule); none of these flags: the constant --learning-rate, as before
+    parser.add_argument('--lr-schedule', type=str, choices=list(LRSchedule.KINDS), default=None,
+                        help='rate after the warm-up: constant | step (x --lr-decay-factor at every --lr-decay-steps) | cosine '
+                             '(down to --lr-final-factor x the rate at --lr-total-steps)')
+    parser.add_argument('--lr-warmup-steps', type=int, default=None, metavar='N',
+                        help='linear warm-up from --lr-warmup-factor x the rate to the rate over the first N updates (default 0)')
+    parser.add_argument('--lr-warmup-factor', type=float, default=None, metavar='F', help='default 1/3')
+    parser.add_argument('--lr-decay-steps', type=int, nargs='+', default=None, metavar='A',
+                        help='with --lr-schedule step: update counts (at most %d, increasing) at which the rate drops' % LRSchedule.MAX_BOUNDARIES)
+    parser.add_argument('--lr-decay-factor', type=float, default=None, metavar='G', help='default 0.1')
+    parser.add_argument('--lr-total-steps', type=int, default=None, metavar='T',
+                        help='update count at which the cosine reaches its floor (default: restored step + epochs x steps per epoch)')
+    parser.add_argument('--lr-final-factor', type=float, default=None, metavar='F', help='default 0')
     return parser
+
+
+LR_FLAGS = ('lr_schedule', 'lr_warmup_steps', 'lr_warmup_factor', 'lr_decay_steps', 'lr_decay_factor', 'lr_total_steps',
+            'lr_final_factor')
+
+
+def lr_flag_error(args):
+    """What is wrong with the --lr-* flags as given (checked before any dataset or device is touched), or None."""
+    kind = args.lr_schedule or 'constant'
+    if args.lr_decay_steps is not None and kind != 'step':
+        return '--lr-decay-steps needs --lr-schedule step'
+    if args.lr_decay_factor is not None and kind != 'step':
+        return '--lr-decay-factor needs --lr-schedule step'
+    if args.lr_final_factor is not None and kind != 'cosine':
+        return '--lr-final-factor needs --lr-schedule cosine'
+    if kind == 'step' and not args.lr_decay_steps:
+        return '--lr-schedule step needs --lr-decay-steps A B ...'
+    if args.lr_decay_steps is not None and len(args.lr_decay_steps) > LRSchedule.MAX_BOUNDARIES:
+        return '--lr-decay-steps: at most %d steps (got %d)' % (LRSchedule.MAX_BOUNDARIES, len(args.lr_decay_steps))
+    if args.lr_total_steps is not None and args.lr_total_steps <= (args.lr_warmup_steps or 0):
+        return '--lr-total-steps %d is not above --lr-warmup-steps %d' % (args.lr_total_steps, args.lr_warmup_steps or 0)
+    return None
+
+
+def schedule_from_args(args, steps_per_epoch, restored_step):
+    """The LRSchedule the --lr-* flags describe, or None when none of them is given (the constant-rate path, unchanged).  Pure:
+    no device, no files.  --lr-total-steps defaults to the update count this run ends at.  Raises ValueError (main: parser.error)
+    for combinations that make no sense."""
+    if all(getattr(args, f) is None for f in LR_FLAGS):
+        return None
+    err = lr_flag_error(args)
+    if err:
+        raise ValueError(err)
+    warmup = args.lr_warmup_steps or 0
+    total = args.lr_total_steps if args.lr_total_steps is not None else int(restored_step) + args.epochs * int(steps_per_epoch)
+    if total <= warmup:
+        raise ValueError('the run ends at update %d, not above --lr-warmup-steps %d (see --lr-total-steps)' % (total, warmup))
+    return LRSchedule(kind=args.lr_schedule or 'constant', base_lr=args.learning_rate, warmup_steps=warmup,
+                      warmup_factor=1.0 / 3.0 if args.lr_warmup_factor is None else args.lr_warmup_factor,
+                      boundaries=tuple(args.lr_decay_steps or ()),
+                      decay_factor=0.1 if args.lr_decay_factor is None else args.lr_decay_factor,
+                      total_steps=total, final_factor=0.0 if args.lr_final_factor is None else args.lr_final_factor)
 
 
 def init_distributed(backend=None):
@@ -1003,6 +1194,8 @@ def main(argv=None):
         parser.error('--augment-crop / --augment-seed need --augment')
     if args.augment_crop is not None and not (0.0 < args.augment_crop <= 1.0):
         parser.error('--augment-crop S: 0 < S <= 1 (got %g)' % args.augment_crop)
+    if lr_flag_error(args):
+        parser.error(lr_flag_error(args))
     K = args.samples_per_step
     if K != 1 and not files:
         parser.error('--samples-per-step groups raw uint8 image files: it needs --dataset pascal ... or coco ...')
@@ -1064,9 +1257,14 @@ def main(argv=None):
                                   **group_kw)
     else:
         feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev)
+    restored = checkpoint.saved_step(path) if (path is not None and os.path.exists(path)) else 0
+    try:
+        lr_schedule = schedule_from_args(args, steps_per_epoch, restored)
+    except ValueError as e:
+        parser.error(str(e))
     trainer = Trainer(net, levels, optimizer=args.optimizer, learning_rate=args.learning_rate,
                       grad_clip_norm=args.grad_clip_norm, loss_mode=args.loss, device=dev, use_graph=not args.no_graph,
-                      input_fn=feed)
+                      input_fn=feed, **({'lr_schedule': lr_schedule} if lr_schedule is not None else {}))
     step = 0
     if path is not None and os.path.exists(path):
         step = checkpoint.load(path, net, trainer)                                 # every rank reads the same file
@@ -1086,9 +1284,9 @@ def main(argv=None):
                 out = trainer.step()                                               # batch = [image, hflip] of a new sample
                 step += 1
                 if step % 20 == 0 and rank == 0:
-                    print('epoch %d step %d class_loss %.4f regr_loss %.4f reg %.4f' % (
-                        epoch, step, out['class_loss'].item(), out['regr_loss'].item(), out['regularization_loss'].item()),
-                        flush=True)
+                    print('epoch %d step %d class_loss %.4f regr_loss %.4f reg %.4f lr %.3g' % (
+                        epoch, step, out['class_loss'].item(), out['regr_loss'].item(), out['regularization_loss'].item(),
+                        trainer.opt.current_lr()), flush=True)                     # (the rate of the NEXT update: host-side, no sync)
             trainer.check_device_errors()
             if args.augment and getattr(loader, 'skipped', 0) != skipped0:
                 raise _rn.RnError("the loader skipped samples while iterating: the augmentation's ordinals no longer equal the "
