@@ -163,9 +163,11 @@ __global__ __launch_bounds__(T) void loss_reduce4_kernel(const LossArgs a) {
         const float zz[4] = {z[u][k].x, z[u][k].y, z[u][k].z, z[u][k].w}, ll[4] = {l[u][k].x, l[u][k].y, l[u][k].z, l[u][k].w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float zv = zz[e], lv = ll[e];
+          // select, not multiply: what a removed row holds (NaN, inf) must not reach a sum as NaN * 0; with finite values the
+          // terms are w * f(0, 0) = 0 as before, so the sums keep their bits
+          const float zv = w != 0.f ? zz[e] : 0.f, lv = w != 0.f ? ll[e] : 0.f;
           const float p = sigmoidf(zv);
-          if (j + 4 * k < CQ) lmax = fmaxf(lmax, lv);
+          if (j + 4 * k < CQ) lmax = fmaxf(lmax, ll[e]);
           if (MODE == RN_LOSS_BCE_DICE) {
             I[k][e] = fmaf(w, lv * p, I[k][e]); L[k][e] = fmaf(w, lv, L[k][e]); P[k][e] = fmaf(w, p, P[k][e]);
             cls = fmaf(w, fmaxf(zv, 0.f) - zv * lv + log1pf(expf(-fabsf(zv))), cls);
