@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 411
+#define RN_API_VERSION 412
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -934,6 +934,28 @@ int rn_lr_schedule_eval(rn_lr_schedule sched, uint64_t* step_dev, float* lr_dev,
 int rn_optimizer_step_norm_lrdev(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
                                  int64_t count, const float* lr_dev, float grad_scale, uint64_t* advance_counter,
                                  uint64_t advance_by, double* partial, rn_stream_t stream);
+/* An exponential moving average of the weights, kept by the pass that updates them (tf.train.ExponentialMovingAverage; the
+ * reference, train.py:111-134, trains and evaluates the raw weights only).  With n = updates applied before this one and w' the
+ * weight after it:
+ *   d(n) = min(decay, (1 + n) / (10 + n))   warmup != 0
+ *        = decay                            warmup == 0
+ *   e   <- e - (e - w') * (1 - d(n))        in fp32, per element
+ * One thread: n = *num_updates_dev;  ema_dev[0] = d(n);  ema_dev[1] = 1 - d(n), each formed in double and rounded to float once;
+ * *num_updates_dev = n + 1.  The count is the average's own device word (a constant-rate step has no step word).  No argument
+ * changes from step to step, so a replayed hipGraph advances the average by itself.  Checked by the entry: 0 < decay < 1,
+ * non-null pointers. */
+int rn_ema_decay_eval(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, rn_stream_t stream);
+/* The optimizer update of train.py:111-134 that also keeps the moving average `ema` (count floats, 16-byte aligned, laid out
+ * like w) with 1 - d(n) read from ema_dev[1] (what rn_ema_decay_eval left there; a launch on another stream must be ordered
+ * behind it).  The union of the three entries above, every part optional as there: the rate is lr_dev[1] when lr_dev is given,
+ * else `lr` (then RN_OPT_ADAM needs step >= 1); clip_norm > 0 needs norm_sq; `partial` (rn_optimizer_norm_pairs(count) pairs,
+ * without clipping only) makes the pass form the slice's share of (sum g'^2, regulariser) as rn_optimizer_step_norm does.
+ * w, the slots, the pairs and the counter come out exactly as from those entries: the average is one more load, one fused
+ * multiply-add and one more store per element (8 B/element). */
+int rn_optimizer_step_ema(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
+                          int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm, const float* norm_sq,
+                          int64_t step, uint64_t* advance_counter, uint64_t advance_by, double* partial, float* ema,
+                          const float* ema_dev, rn_stream_t stream);
 /* *counter += inc on the stream (the same counter, for callers that run backward passes without an optimizer step) */
 int rn_counter_add(uint64_t* counter, uint64_t inc, rn_stream_t stream);
 /* p[0..count) = 0 (16-byte aligned): the gradient arena before a backward pass (the reference's graph zero-initialises

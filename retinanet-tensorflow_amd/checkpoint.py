@@ -3,6 +3,7 @@ model's parameter names (the reference delegates this to tf.estimator, train.py:
 save_checkpoints_steps; no custom format exists to be compatible with)."""
 import json
 import os
+import sys
 
 import torch
 from safetensors import safe_open
@@ -11,7 +12,9 @@ from safetensors.torch import save_file
 
 def save(path, net, trainer=None, step=0, extra=None):
     """Weights under "model/<name>"; optimizer slots PER PARAMETER under "optimizer/state{1,2}/<name>" (independent of the
-    arena's layout); the dropout step counter, so that a resumed run does not replay the masks of step 0."""
+    arena's layout); the dropout step counter, so that a resumed run does not replay the masks of step 0.  A trainer that keeps a
+    moving average of the weights adds it PER PARAMETER under "ema/<name>" with metadata ema_decay / ema_warmup / ema_updates
+    ("model/<name>" stays the raw weights: resuming needs them); readers that know nothing of these keys ignore them."""
     tensors = {"model/" + k: v.detach().cpu().contiguous().clone() for k, v in net.named_parameters()}
     meta = {"step": str(int(step)), "format": "retinanet-amd-v2"}
     if trainer is not None:
@@ -24,6 +27,11 @@ def save(path, net, trainer=None, step=0, extra=None):
         # (stored without this replica's offset: every rank adds its own back on load, replicas keep distinct dropout streams)
         tensors["trainer/drop_counter"] = trainer.drop_counter.detach().cpu().clone() - int(getattr(trainer, "drop_rank_offset", 0))
         meta.update(optimizer=trainer.opt.kind, step_count=str(trainer.opt.step_count))
+        if getattr(trainer.opt, "ema", None) is not None:
+            for p, (off, size) in zip(trainer.arena.params, trainer.arena.offsets):
+                tensors["ema/" + names[id(p)]] = trainer.opt.ema[off:off + size].detach().cpu().clone().view(p.shape)
+            meta.update(ema_decay=repr(trainer.opt.ema_decay), ema_warmup=str(int(trainer.opt.ema_warmup)),
+                        ema_updates=str(int(trainer.opt.ema_updates_dev.item())))
     if extra:
         meta["extra"] = json.dumps(extra)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -45,9 +53,17 @@ def saved_step(path):
         return int((f.metadata() or {}).get("step", 0))
 
 
-def load(path, net, trainer=None):
+_seeded_note = [False]
+
+
+def load(path, net, trainer=None, use_ema=False):
     """Restores in place (the parameters keep pointing into the trainer's arena).  Returns the saved step.
-    Missing keys and shape mismatches raise a ValueError that names the parameter."""
+    Missing keys and shape mismatches raise a ValueError that names the parameter.
+
+    A trainer that keeps a moving average gets "ema/<name>" and the update word back; from a file without any "ema/" key (a run
+    that kept none) the average is seeded with the loaded weights and the word with step_count, said once on stderr.  A trainer
+    that keeps none ignores the keys.  use_ema=True (trainer=None): the net is given the AVERAGES instead of the raw weights, for
+    inference; a file without them raises a ValueError."""
     with safe_open(path, framework="pt") as f:
         meta = f.metadata() or {}
         keys = set(f.keys())
@@ -62,12 +78,22 @@ def load(path, net, trainer=None):
                 for pre in need:
                     if pre + k not in keys:
                         raise ValueError("checkpoint %s has no tensor %r" % (path, pre + k))
+        has_ema = any(k.startswith("ema/") for k in keys)
+        if use_ema:
+            if trainer is not None:
+                raise ValueError("checkpoint.load(use_ema=True) puts the averages into a net for inference: pass no trainer")
+            if not has_ema:
+                raise ValueError("checkpoint %s holds no moving average of the weights (no 'ema/' tensors): it was written "
+                                 "without --ema-decay" % path)
+        want_ema = trainer is not None and getattr(trainer.opt, "ema", None) is not None
+        prefixes = ["ema/" if use_ema else "model/"] + (["ema/"] if want_ema and has_ema else [])
         for k, p in net.named_parameters():
-            if "model/" + k not in keys:
-                raise ValueError("checkpoint %s has no tensor %r" % (path, "model/" + k))
-            shape = tuple(f.get_slice("model/" + k).get_shape())
-            if shape != tuple(p.shape):
-                raise ValueError("checkpoint %s: %r has shape %s, the model expects %s" % (path, "model/" + k, shape, tuple(p.shape)))
+            for pre in prefixes:
+                if pre + k not in keys:
+                    raise ValueError("checkpoint %s has no tensor %r" % (path, pre + k))
+                shape = tuple(f.get_slice(pre + k).get_shape())
+                if shape != tuple(p.shape):
+                    raise ValueError("checkpoint %s: %r has shape %s, the model expects %s" % (path, pre + k, shape, tuple(p.shape)))
 
         def get(key, like):
             if key not in keys:
@@ -79,7 +105,7 @@ def load(path, net, trainer=None):
 
         with torch.no_grad():
             for k, p in net.named_parameters():
-                p.copy_(get("model/" + k, p).to(p.device))
+                p.copy_(get(("ema/" if use_ema else "model/") + k, p).to(p.device))
             if trainer is not None and meta.get("optimizer") is not None:
                 if meta.get("optimizer") != trainer.opt.kind:
                     raise ValueError("checkpoint optimizer %s != %s" % (meta.get("optimizer"), trainer.opt.kind))
@@ -94,6 +120,21 @@ def load(path, net, trainer=None):
                                                .to(trainer.drop_counter.device))
                 # (also the device step word of a learning-rate schedule: a resumed run continues the schedule where it stopped)
                 trainer.opt.set_step_count(int(meta.get("step_count", 0)))
+            if want_ema:
+                opt = trainer.opt
+                if has_ema:
+                    names = {id(p): k for k, p in net.named_parameters()}
+                    for p, (off, size) in zip(trainer.arena.params, trainer.arena.offsets):
+                        opt.ema[off:off + size].copy_(get("ema/" + names[id(p)], p).reshape(-1).to(opt.ema.device))
+                    opt.ema_updates_dev.fill_(int(meta.get("ema_updates", meta.get("step_count", 0))))
+                else:
+                    # written by a run that kept no average: it starts here, at the loaded weights
+                    opt.ema.copy_(trainer.arena.weights)
+                    opt.ema_updates_dev.fill_(int(meta.get("step_count", 0)))
+                    if not _seeded_note[0]:
+                        _seeded_note[0] = True
+                        print("[checkpoint] %s holds no moving average of the weights: it starts from the loaded weights, at update %d"
+                              % (path, int(meta.get("step_count", 0))), file=sys.stderr, flush=True)
     import ops_f16
     ops_f16.weights_changed()
     return int(meta.get("step", 0))

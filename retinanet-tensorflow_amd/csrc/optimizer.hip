@@ -2,7 +2,7 @@
 //   g' = grad*grad_scale + wd*w            (L2 regulariser gradient, scale per parameter)
 //   g' *= clip/max(||g'||, clip)           (tf.clip_by_global_norm, optional)
 //   Momentum(0.9) | RMSProp(0.9, 0.9, 1e-10) | Adam(0.9, 0.999, 1e-8)   [TF-sem]
-// HBM-bound: one pass, float4 accesses; 16-20 B/element.
+// HBM-bound: one pass, float4 accesses; 16-20 B/element (+8 with the moving average of the weights kept by the same pass).
 #include "rn_common.h"
 
 namespace {
@@ -44,15 +44,21 @@ __global__ void norm_reg_finalize_kernel(const double* __restrict__ partial, int
 
 // NORM: the pass that applies the update also forms this launch's share of (sum g'^2, L2 regulariser value) -- both at the
 // weights BEFORE the update, as rn_grad_norm_l2reg does -- into partial[block] (no clipping then: the norm is not an input)
-template <int KIND, bool NORM>
+// EMA: the pass also keeps the exponential moving average of the weights (tf.train.ExponentialMovingAverage): with w' the
+// weight this launch stores and om = ema_dev[1] = 1 - d(n), what rn_ema_decay_eval left on the device, e <- e - (e - w') * om.
+// The trailing two arguments are not read by the EMA = false instantiations.
+template <int KIND, bool NORM, bool EMA>
 __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                      float* __restrict__ s1, float* __restrict__ s2,
                                                      const float* __restrict__ wd, int64_t count, float lr, float gs,
                                                      float clip, const float* __restrict__ norm_sq, unsigned long long* advance, unsigned long long advance_by,
-                                                     double* __restrict__ partial, const float* __restrict__ lr_dev) {
+                                                     double* __restrict__ partial, const float* __restrict__ lr_dev,
+                                                     float* __restrict__ ema, const float* __restrict__ ema_dev) {
   __shared__ double red[2][T / 64];
   double n2 = 0.0, rg = 0.0;
   if (lr_dev) lr = lr_dev[1];  // the rate rn_lr_schedule_eval left on the device: one uniform load per wave, ahead of the loop
+  float om = 0.f;
+  if (EMA) om = ema_dev[1];  // 1 - d(n) of this update, likewise
   if (advance && blockIdx.x == 0 && threadIdx.x == 0) *advance += advance_by;  // the step counter the dropout masks hash (fresh masks next step)
   float cs = 1.f;
   if (clip > 0.f) {
@@ -67,7 +73,9 @@ __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, cons
     float4 av = *reinterpret_cast<float4*>(s1 + i * 4);
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (KIND != RN_OPT_MOMENTUM) bv = *reinterpret_cast<float4*>(s2 + i * 4);
-    float* wp = &wv.x; const float* gp = &gv.x; float* ap = &av.x; float* bp = &bv.x;
+    float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (EMA) ev = *reinterpret_cast<float4*>(ema + i * 4);
+    float* wp = &wv.x; const float* gp = &gv.x; float* ap = &av.x; float* bp = &bv.x; float* ep = &ev.x;
     if (NORM) {
       const float t0 = gv.x * gs + d * wv.x, t1 = gv.y * gs + d * wv.y, t2 = gv.z * gs + d * wv.z, t3 = gv.w * gs + d * wv.w;
       n2 += (double)(t0 * t0 + t1 * t1 + t2 * t2 + t3 * t3);
@@ -88,10 +96,12 @@ __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, cons
         bp[j] = 0.999f * bp[j] + 0.001f * gg * gg;
         wp[j] -= lr * ap[j] / (sqrtf(bp[j]) + 1e-8f);  // lr already carries the bias correction
       }
+      if (EMA) ep[j] -= (ep[j] - wp[j]) * om;
     }
     *reinterpret_cast<float4*>(w + i * 4) = wv;
     *reinterpret_cast<float4*>(s1 + i * 4) = av;
     if (KIND != RN_OPT_MOMENTUM) *reinterpret_cast<float4*>(s2 + i * 4) = bv;
+    if (EMA) *reinterpret_cast<float4*>(ema + i * 4) = ev;
   }
   if (NORM) {
     n2 = rn::wave_sum_d(n2); rg = rn::wave_sum_d(rg);
@@ -134,9 +144,10 @@ extern "C" int rn_grad_norm_l2reg(const float* w, const float* grad, const float
 
 namespace {
 // lr_dev (optional): the kernel reads its rate from lr_dev[1] -- bias correction included -- and `lr` / `step` are not used
+// ema + ema_dev (optional, both or neither): the EMA instantiations, which also keep the moving average of the weights
 int launch_opt(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block, int64_t count, float lr,
                float grad_scale, float clip_norm, const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
-               double* partial, hipStream_t st, const float* lr_dev = nullptr) {
+               double* partial, hipStream_t st, const float* lr_dev = nullptr, float* ema = nullptr, const float* ema_dev = nullptr) {
   RN_CHECK_ARG(w && grad && state1 && wd_per_block, "optimizer: null pointer");
   RN_CHECK_ARG(count > 0 && count % RN_OPT_BLOCK == 0, "optimizer: count %lld not a multiple of %d", (long long)count,
                RN_OPT_BLOCK);
@@ -151,17 +162,21 @@ int launch_opt(int kind, float* w, const float* grad, float* state1, float* stat
     rn::set_error("optimizer: unknown kind %d", kind);
     return RN_EINVAL;
   }
-#define RN_OPT_LAUNCH(KIND_)                                                                                                  \
-  do {                                                                                                                        \
-    if (partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true>), dim3(nb), dim3(T), 0, st, w, grad, state1, state2, wd_per_block, count, lr_eff, \
-                                    grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter, (unsigned long long)advance_by, partial, lr_dev); \
-    else hipLaunchKernelGGL((opt_step_kernel<KIND_, false>), dim3(nb), dim3(T), 0, st, w, grad, state1, state2, wd_per_block, count, lr_eff, \
-                            grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter, (unsigned long long)advance_by, partial, lr_dev); \
+#define RN_OPT_ARGS                                                                                                            \
+  w, grad, state1, state2, wd_per_block, count, lr_eff, grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter,      \
+      (unsigned long long)advance_by, partial, lr_dev, ema, ema_dev
+#define RN_OPT_LAUNCH(KIND_)                                                                                                    \
+  do {                                                                                                                          \
+    if (ema && partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);        \
+    else if (ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);             \
+    else if (partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);         \
+    else hipLaunchKernelGGL((opt_step_kernel<KIND_, false, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);                     \
   } while (0)
   if (kind == RN_OPT_MOMENTUM) RN_OPT_LAUNCH(RN_OPT_MOMENTUM);
   else if (kind == RN_OPT_RMSPROP) RN_OPT_LAUNCH(RN_OPT_RMSPROP);
   else RN_OPT_LAUNCH(RN_OPT_ADAM);
 #undef RN_OPT_LAUNCH
+#undef RN_OPT_ARGS
   RN_LAUNCH_CHECK();
   return RN_OK;
 }
@@ -191,6 +206,38 @@ extern "C" int rn_optimizer_step_norm_lrdev(int kind, float* w, const float* gra
   RN_CHECK_ARG(lr_dev, "optimizer step + norm: null device rate");
   return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, 0.f, grad_scale, 0.f, nullptr, 0, advance_counter, advance_by,
                     partial, (hipStream_t)stream, lr_dev);
+}
+
+extern "C" int rn_optimizer_step_ema(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
+                                     int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm,
+                                     const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
+                                     double* partial, float* ema, const float* ema_dev, rn_stream_t stream) {
+  RN_CHECK_ARG(ema && ema_dev, "optimizer step + ema: null ema / ema_dev");
+  RN_CHECK_ARG(((uintptr_t)ema & 15) == 0, "optimizer step + ema: ema is not 16-byte aligned");
+  RN_CHECK_ARG(!(partial && clip_norm > 0.f), "optimizer step + ema: the fused norm (partial) is formed without clipping");
+  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter,
+                    advance_by, partial, (hipStream_t)stream, lr_dev, ema, ema_dev);
+}
+
+namespace {
+// d(n) of rn_ema_decay_eval (include/rn_hip.h) and its complement, each formed in double and rounded to float once
+__global__ void ema_decay_eval_kernel(double decay, int warmup, unsigned long long* num_updates_dev, float* ema_dev) {
+  const unsigned long long n = *num_updates_dev;
+  double d = decay;
+  if (warmup) d = fmin(decay, (1.0 + (double)n) / (10.0 + (double)n));
+  ema_dev[0] = (float)d;
+  ema_dev[1] = (float)(1.0 - d);
+  *num_updates_dev = n + 1;
+}
+}  // namespace
+
+extern "C" int rn_ema_decay_eval(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, rn_stream_t stream) {
+  RN_CHECK_ARG(num_updates_dev && ema_dev, "ema_decay_eval: null pointer");
+  RN_CHECK_ARG(decay > 0.0 && decay < 1.0, "ema_decay_eval: decay %g outside (0, 1)", decay);
+  hipLaunchKernelGGL(ema_decay_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, decay, warmup, (unsigned long long*)num_updates_dev,
+                     ema_dev);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
 }
 
 namespace {

@@ -165,9 +165,16 @@ class Optimizer(object):
     `schedule` (LRSchedule): the rate of update s is schedule.value(s); `lr` stays the base rate.  On a device arena without
     clipping the rate never passes through the host: begin_step launches rn_lr_schedule_eval, which reads the device step word
     `step_dev`, leaves [lr(s), the rate the update multiplies by] in `lr_dev` and advances the word; the slices' update kernels read
-    lr_dev[1].  No launch argument of such a step changes from one step to the next, Adam's bias correction included."""
+    lr_dev[1].  No launch argument of such a step changes from one step to the next, Adam's bias correction included.
 
-    def __init__(self, arena, kind='momentum', learning_rate=1e-2, grad_clip_norm=None, schedule=None):
+    `ema_decay` D (0 < D < 1; device arena): `ema` holds an exponential moving average of the weights with
+    tf.train.ExponentialMovingAverage's semantics, kept by the update kernel itself -- with n = updates applied before this one and
+    w' the weight after it, e <- e - (e - w') * (1 - d(n)), d(n) = min(D, (1 + n) / (10 + n)) (`ema_warmup`) or D.  n is the
+    average's own device word `ema_updates_dev`: begin_step launches rn_ema_decay_eval, which leaves [d(n), 1 - d(n)] in `ema_dev`
+    and advances the word, so this too adds no launch argument that changes from step to step."""
+
+    def __init__(self, arena, kind='momentum', learning_rate=1e-2, grad_clip_norm=None, schedule=None, ema_decay=None,
+                 ema_warmup=True):
         assert kind in ['momentum', 'adam', 'rmsprop']
         self.arena, self.kind, self.lr = arena, kind, float(learning_rate)
         self.clip = float(grad_clip_norm) if grad_clip_norm is not None else 0.0
@@ -182,6 +189,17 @@ class Optimizer(object):
             self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)        # (the kernel's uint64: same bits)
             self.lr_dev = torch.zeros(2, dtype=torch.float32, device=dev)
             self._sched_struct = schedule.struct()
+        # the moving average and its two device words: HERE as well, for the same reason (e starts as the weights as they are now)
+        self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
+        self.ema = self.ema_updates_dev = self.ema_dev = None
+        if self.ema_decay is not None:
+            if not 0.0 < self.ema_decay < 1.0:
+                raise ValueError("ema_decay %r is not inside (0, 1)" % (ema_decay,))
+            if dev.type != 'cuda':
+                raise _rn.RnError("the moving average of the weights is kept by the device's update kernel: it needs a device arena")
+            self.ema = arena.weights.clone()
+            self.ema_updates_dev = torch.zeros(1, dtype=torch.int64, device=dev)    # (the kernel's uint64: same bits)
+            self.ema_dev = torch.zeros(2, dtype=torch.float32, device=dev)
         self.state1 = torch.ones_like(arena.weights) if kind == 'rmsprop' else torch.zeros_like(arena.weights)
         self.state2 = torch.zeros_like(arena.weights) if kind != 'momentum' else None
         self.norm_reg = torch.zeros(2, dtype=torch.float32, device=dev)   # [sum g'^2, L2 reg loss]
@@ -210,6 +228,19 @@ class Optimizer(object):
                   'rn_grad_norm_l2reg')
         lr = self.current_lr()           # (the rate is a launch argument of this path: a schedule is evaluated on the host)
         self.step_count += 1
+        if self.ema is not None:
+            _rn.check(L_.rn_ema_decay_eval(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(), _rn.f32(self.ema_dev),
+                                           _rn.stream()), 'rn_ema_decay_eval')
+            _rn.check(L_.rn_optimizer_step_ema(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
+                                               _rn.f32(self.state2) if self.state2 is not None else None,
+                                               _rn.f32(a.wd_per_block), a.count, lr, None, grad_scale, self.clip,
+                                               _rn.f32(self.norm_reg), self.step_count,
+                                               advance_counter.data_ptr() if advance_counter is not None else None,
+                                               ops.DROPOUT_COUNTER_STEP, None, _rn.f32(self.ema), _rn.f32(self.ema_dev), _rn.stream()),
+                      'rn_optimizer_step_ema')
+            import ops_f16
+            ops_f16.weights_changed()
+            return
         _rn.check(L_.rn_optimizer_step(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
                                        _rn.f32(self.state2) if self.state2 is not None else None,
                                        _rn.f32(a.wd_per_block), a.count, lr, grad_scale, self.clip,
@@ -229,7 +260,12 @@ class Optimizer(object):
             # this update's rate, on the main stream ahead of every slice; the kernel advances step_dev itself
             _rn.check(_rn.lib().rn_lr_schedule_eval(self._sched_struct, self.step_dev.data_ptr(), _rn.f32(self.lr_dev),
                                                     _rn.OPT[self.kind], _rn.stream()), 'rn_lr_schedule_eval')
-            self._sched_event = torch.cuda.Event()
+        if self.ema is not None:
+            # 1 - d(n) of this update, beside the rate; the kernel advances ema_updates_dev itself
+            _rn.check(_rn.lib().rn_ema_decay_eval(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(),
+                                                  _rn.f32(self.ema_dev), _rn.stream()), 'rn_ema_decay_eval')
+        if self.lr_dev is not None or self.ema is not None:
+            self._sched_event = torch.cuda.Event()       # one event behind both one-thread kernels
             self._sched_event.record()
 
     def step_slice(self, lo, hi, grad_scale, advance_counter=None, stream=None):
@@ -239,11 +275,22 @@ class Optimizer(object):
         assert 2 * (self._pairs + npairs) <= self._partial.numel()
         part = self._partial[2 * self._pairs:]
         self._pairs += npairs
+        if (self.lr_dev is not None or self.ema is not None) and stream is not None:
+            # a slice on another stream reads lr_dev / ema_dev too: behind the one-thread kernels, not the whole main stream
+            other = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(getattr(stream, 'value', stream)))
+            other.wait_event(self._sched_event)
+            stream = ctypes.c_void_p(other.cuda_stream)
+        if self.ema is not None:
+            _rn.check(L_.rn_optimizer_step_ema(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(),
+                                               self.state1[lo:].data_ptr(),
+                                               self.state2[lo:].data_ptr() if self.state2 is not None else None,
+                                               a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), hi - lo, self.lr,
+                                               _rn.f32(self.lr_dev) if self.lr_dev is not None else None, grad_scale, 0.0, None,
+                                               self.step_count, advance_counter.data_ptr() if advance_counter is not None else None,
+                                               ops.DROPOUT_COUNTER_STEP, part.data_ptr(), self.ema[lo:].data_ptr(), _rn.f32(self.ema_dev),
+                                               stream if stream is not None else _rn.stream()), 'rn_optimizer_step_ema')
+            return
         if self.lr_dev is not None:
-            if stream is not None:       # a slice on another stream reads lr_dev too: behind the schedule kernel, not the whole main stream
-                other = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(getattr(stream, 'value', stream)))
-                other.wait_event(self._sched_event)
-                stream = ctypes.c_void_p(other.cuda_stream)
             _rn.check(L_.rn_optimizer_step_norm_lrdev(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(),
                                                       self.state1[lo:].data_ptr(),
                                                       self.state2[lo:].data_ptr() if self.state2 is not None else None,
@@ -273,6 +320,15 @@ class Optimizer(object):
         self.step_count = int(n)
         if self.step_dev is not None:
             self.step_dev.fill_(self.step_count)
+        if self.ema_updates_dev is not None:
+            self.ema_updates_dev.fill_(self.step_count)
+
+    def ema_decay_value(self, n):
+        """d(n), the decay of the update that follows n applied ones, in float64: the host's copy of what rn_ema_decay_eval forms."""
+        if self.ema_decay is None:
+            raise ValueError("this optimizer keeps no moving average (ema_decay=None)")
+        n = int(n)
+        return min(self.ema_decay, (1.0 + n) / (10.0 + n)) if self.ema_warmup else self.ema_decay
 
     @property
     def regularization_loss(self):
@@ -402,7 +458,8 @@ class Trainer(object):
     def __init__(self, net, levels=None, optimizer='momentum', learning_rate=1e-2, grad_clip_norm=None,
                  loss_mode='bce_dice', device='cuda', use_graph=False, process_group=None,
                  direct_param_grads=True, wgrad_side_stream=False, defer_reductions=True, overlap=True,
-                 force_collective=False, input_fn=None, check_interval=50, capture_collectives=None, lr_schedule=None):
+                 force_collective=False, input_fn=None, check_interval=50, capture_collectives=None, lr_schedule=None,
+                 ema_decay=None, ema_warmup=True):
         self.net, self.levels = net, levels or build_levels()
         self.device = torch.device(device)
         if self.device.type == 'cuda':
@@ -417,7 +474,11 @@ class Trainer(object):
         self.arena = ParamArena(net, self.device)
         # lr_schedule (LRSchedule): the rate lives on the device and advances inside the step (Optimizer docstring); None: the
         # constant `learning_rate`, a launch argument
-        self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule)
+        # ema_decay: the update kernel also keeps a moving average of the weights (Optimizer docstring; ema_weights() runs the net
+        # on it).  Its decay is read from the device like a scheduled rate: no host scalar, so nothing about the one-graph step or
+        # its cache key changes
+        ema_kw = {} if ema_decay is None else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}
+        self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule, **ema_kw)
         self.allreduce = GradientAllReduce(self.arena, process_group, force=force_collective)
         self.use_graph = use_graph
         self.input_fn = input_fn       # optional: features = input_fn(), run INSIDE segment A (e.g. device-side label assignment)
@@ -942,6 +1003,29 @@ class Trainer(object):
                      'regularization_loss': self.opt.regularization_loss}
         return self.last
 
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the net runs on the moving average: the contents of arena.weights and opt.ema are swapped on the
+        device (the net's parameters are views of the arena), and swapped back on the way out, also after an exception.  Do not
+        train inside it."""
+        import ops_f16
+        if self.opt.ema is None:
+            raise ValueError("this trainer keeps no moving average of the weights: build it with ema_decay=D (--ema-decay D)")
+        if self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise _rn.RnError("ema_weights() swaps the weights on the device: not while a stream is capturing")
+
+        def swap():
+            with torch.no_grad():
+                tmp = self.arena.weights.clone()
+                self.arena.weights.copy_(self.opt.ema)
+                self.opt.ema.copy_(tmp)
+            ops_f16.weights_changed()
+        swap()
+        try:
+            yield self.net
+        finally:
+            swap()
+
     def allreduce_exposed_ms(self):
         """Mean time the compute stream waited for collectives after the last backward kernel (needs timing = {})."""
         ev = (self.timing or {}).get('exposed_events', [])
@@ -1094,7 +1178,22 @@ def build_parser():
     parser.add_argument('--lr-total-steps', type=int, default=None, metavar='T',
                         help='update count at which the cosine reaches its floor (default: restored step + epochs x steps per epoch)')
     parser.add_argument('--lr-final-factor', type=float, default=None, metavar='F', help='default 0')
+    # moving average of the weights (Optimizer docstring); without --ema-decay: none, as before
+    parser.add_argument('--ema-decay', type=float, default=None, metavar='D',
+                        help='keep an exponential moving average of the weights inside the step (0 < D < 1, e.g. 0.9998); it is '
+                             'stored in the checkpoint and evaluated beside the raw weights')
+    parser.add_argument('--ema-no-warmup', action='store_true',
+                        help='with --ema-decay: the decay is D from the first update on instead of min(D, (1 + n) / (10 + n))')
     return parser
+
+
+def ema_flag_error(args):
+    """What is wrong with the --ema-* flags as given (checked before any dataset or device is touched), or None."""
+    if args.ema_no_warmup and args.ema_decay is None:
+        return '--ema-no-warmup needs --ema-decay'
+    if args.ema_decay is not None and not 0.0 < args.ema_decay < 1.0:
+        return '--ema-decay D: 0 < D < 1 (got %g)' % args.ema_decay
+    return None
 
 
 LR_FLAGS = ('lr_schedule', 'lr_warmup_steps', 'lr_warmup_factor', 'lr_decay_steps', 'lr_decay_factor', 'lr_total_steps',
@@ -1171,6 +1270,8 @@ def broadcast_initial_state(trainer, src=0):
         dist.broadcast(trainer.opt.state1, src=src)
         if trainer.opt.state2 is not None:
             dist.broadcast(trainer.opt.state2, src=src)
+        if trainer.opt.ema is not None:
+            dist.broadcast(trainer.opt.ema, src=src)
 
 
 LAST_RUN = {}
@@ -1196,6 +1297,8 @@ def main(argv=None):
         parser.error('--augment-crop S: 0 < S <= 1 (got %g)' % args.augment_crop)
     if lr_flag_error(args):
         parser.error(lr_flag_error(args))
+    if ema_flag_error(args):
+        parser.error(ema_flag_error(args))
     K = args.samples_per_step
     if K != 1 and not files:
         parser.error('--samples-per-step groups raw uint8 image files: it needs --dataset pascal ... or coco ...')
@@ -1264,7 +1367,8 @@ def main(argv=None):
         parser.error(str(e))
     trainer = Trainer(net, levels, optimizer=args.optimizer, learning_rate=args.learning_rate,
                       grad_clip_norm=args.grad_clip_norm, loss_mode=args.loss, device=dev, use_graph=not args.no_graph,
-                      input_fn=feed, **({'lr_schedule': lr_schedule} if lr_schedule is not None else {}))
+                      input_fn=feed, **({'lr_schedule': lr_schedule} if lr_schedule is not None else {}),
+                      **({'ema_decay': args.ema_decay, 'ema_warmup': not args.ema_no_warmup} if args.ema_decay is not None else {}))
     step = 0
     if path is not None and os.path.exists(path):
         step = checkpoint.load(path, net, trainer)                                 # every rank reads the same file
@@ -1308,6 +1412,15 @@ def main(argv=None):
         res = evaluate(net, eval_loader, levels, args.eval_images, scale=args.scale, device=dev)
         print('eval: mAP %.4f AP50 %.4f AP75 %.4f class_iou %.4f regr_iou %.4f over %d images' % (
             res['mAP'], res['AP50'], res['AP75'], res['class_iou'], res['regr_iou'], res['images']), flush=True)
+        if trainer.opt.ema is not None:
+            if args.eval_dataset:
+                eval_loader = Inferred(args.eval_dataset[0], args.eval_dataset[1:])        # (a fresh loader: the same samples again)
+            else:
+                eval_loader = Shapes(None, image_size=(args.scale + args.scale // 4, args.scale), seed=12345)
+            with trainer.ema_weights():
+                res = evaluate(net, eval_loader, levels, args.eval_images, scale=args.scale, device=dev)
+            print('eval (ema): mAP %.4f AP50 %.4f AP75 %.4f class_iou %.4f regr_iou %.4f over %d images' % (
+                res['mAP'], res['AP50'], res['AP75'], res['class_iou'], res['regr_iou'], res['images']), flush=True)
     if started:
         import torch.distributed as dist
         dist.barrier()
