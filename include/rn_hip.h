@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 412
+#define RN_API_VERSION 413
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -956,6 +956,38 @@ int rn_optimizer_step_ema(int kind, float* w, const float* grad, float* state1, 
                           int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm, const float* norm_sq,
                           int64_t step, uint64_t* advance_counter, uint64_t advance_by, double* partial, float* ema,
                           const float* ema_dev, rn_stream_t stream);
+/* Gradient accumulation inside the captured step (the reference takes one optimizer step per batch, train.py:111-134; a larger
+ * effective batch than fits in memory is the usual reason to sum the gradients of A batches first).  A = accumulate_steps; a
+ * micro-step is one forward + backward pass, an update is applied on every A-th micro-step, from the MEAN of the last A gradients.
+ * GroupNorm is per sample, so that mean is the gradient of the A-times-larger batch (but for the dropout masks, drawn per
+ * micro-step).  The backward kernels overwrite a parameter's gradient slot, so the sum has an arena of its own, `acc`, kept by the
+ * pass that reads the gradients anyway.
+ * One thread: p = *micro_dev % A;  accum_dev[0] = p;  accum_dev[1] = (p == A - 1);  *micro_dev += 1.  No argument changes from
+ * micro-step to micro-step, so ONE replayed hipGraph serves every phase.  Checked by the entry: A >= 1, non-null pointers. */
+int rn_accum_phase_eval(int32_t accumulate_steps, uint64_t* micro_dev, int32_t* accum_dev, rn_stream_t stream);
+/* rn_lr_schedule_eval / rn_ema_decay_eval behind the gate accum_dev[1] (what rn_accum_phase_eval left there): the same kernel
+ * body and the same argument checks when it is non-zero; otherwise NOTHING -- lr_dev / ema_dev and the step / update word stay as
+ * they are, so both count updates, not micro-steps.  accum_dev must not be null. */
+int rn_lr_schedule_eval_gated(rn_lr_schedule sched, uint64_t* step_dev, float* lr_dev, int optimizer_kind, const int32_t* accum_dev,
+                              rn_stream_t stream);
+int rn_ema_decay_eval_gated(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, const int32_t* accum_dev,
+                            rn_stream_t stream);
+/* The fused-norm update (rn_optimizer_step_norm / _lrdev / _ema without clipping: `partial` is required; the rate is lr_dev[1] when
+ * lr_dev is given, else `lr`, then RN_OPT_ADAM needs step >= 1; ema + ema_dev both or neither) on an accumulated gradient.  Every
+ * wave reads accum_dev[0..1] = [p, applying] once and the launch runs ONE of three loops, fp32 per element, gs = grad_scale:
+ *   p == 0, not applying   acc  = grad * gs                 acc is not read                              8 B/element
+ *   p  > 0, not applying   acc += grad * gs                                                              12 B/element
+ *   applying               G = (acc + grad * gs) * inv_accum;  g' = G + wd*w;  the update, the average and the (sum g'^2,
+ *                          regulariser) pair exactly as the entries above form them from g'; acc is not written (the next
+ *                          cycle's first launch overwrites it)                                           +4 B/element
+ * A launch that does not apply leaves w, the slots, ema and its `partial` pairs untouched: rn_norm_reg_finalize then gives the
+ * LAST update's (sum g'^2, regulariser) again.  advance_counter is bumped by every launch (fresh dropout masks per micro-step).
+ * acc: count floats, 16-byte aligned, laid out like w; zero-filled at the start.  Checked by the entry: what rn_optimizer_step_ema
+ * checks, plus non-null acc / accum_dev / partial and 0 < inv_accum <= 1 (the caller passes 1 / A). */
+int rn_optimizer_step_accum(int kind, float* w, const float* grad, float* acc, float* state1, float* state2,
+                            const float* wd_per_block, int64_t count, float lr, const float* lr_dev, float grad_scale,
+                            float inv_accum, const int32_t* accum_dev, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
+                            double* partial, float* ema, const float* ema_dev, rn_stream_t stream);
 /* *counter += inc on the stream (the same counter, for callers that run backward passes without an optimizer step) */
 int rn_counter_add(uint64_t* counter, uint64_t inc, rn_stream_t stream);
 /* p[0..count) = 0 (16-byte aligned): the gradient arena before a backward pass (the reference's graph zero-initialises

@@ -14,7 +14,10 @@ def save(path, net, trainer=None, step=0, extra=None):
     """Weights under "model/<name>"; optimizer slots PER PARAMETER under "optimizer/state{1,2}/<name>" (independent of the
     arena's layout); the dropout step counter, so that a resumed run does not replay the masks of step 0.  A trainer that keeps a
     moving average of the weights adds it PER PARAMETER under "ema/<name>" with metadata ema_decay / ema_warmup / ema_updates
-    ("model/<name>" stays the raw weights: resuming needs them); readers that know nothing of these keys ignore them."""
+    ("model/<name>" stays the raw weights: resuming needs them); readers that know nothing of these keys ignore them.  A trainer
+    that accumulates gradients (accumulate_steps A > 1) adds the cycle's running sum PER PARAMETER under "accum/<name>" with metadata
+    accum_steps = A and accum_micro = micro-steps taken, so a checkpoint written in the middle of a cycle resumes exactly.  `step`
+    counts micro-steps (the position in the sample stream depends on it), step_count counts updates."""
     tensors = {"model/" + k: v.detach().cpu().contiguous().clone() for k, v in net.named_parameters()}
     meta = {"step": str(int(step)), "format": "retinanet-amd-v2"}
     if trainer is not None:
@@ -32,6 +35,10 @@ def save(path, net, trainer=None, step=0, extra=None):
                 tensors["ema/" + names[id(p)]] = trainer.opt.ema[off:off + size].detach().cpu().clone().view(p.shape)
             meta.update(ema_decay=repr(trainer.opt.ema_decay), ema_warmup=str(int(trainer.opt.ema_warmup)),
                         ema_updates=str(int(trainer.opt.ema_updates_dev.item())))
+        if getattr(trainer.opt, "acc", None) is not None:
+            for p, (off, size) in zip(trainer.arena.params, trainer.arena.offsets):
+                tensors["accum/" + names[id(p)]] = trainer.opt.acc[off:off + size].detach().cpu().clone().view(p.shape)
+            meta.update(accum_steps=str(trainer.opt.accumulate_steps), accum_micro=str(int(trainer.opt.micro_dev.item())))
     if extra:
         meta["extra"] = json.dumps(extra)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -53,7 +60,17 @@ def saved_step(path):
         return int((f.metadata() or {}).get("step", 0))
 
 
+def saved_updates(path, accumulate_steps):
+    """(updates applied, micro-steps into the unfinished cycle) as a run with `accumulate_steps` resumes from this checkpoint,
+    without reading a tensor: the phase is 0 unless the file was written with the same accumulate_steps (see load)."""
+    with safe_open(path, framework="pt") as f:
+        meta = f.metadata() or {}
+    same = int(meta.get("accum_steps", 1)) == int(accumulate_steps) and "accum_micro" in meta
+    return int(meta.get("step_count", 0)), (int(meta["accum_micro"]) % int(accumulate_steps) if same else 0)
+
+
 _seeded_note = [False]
+_fresh_cycle_note = [False]
 
 
 def load(path, net, trainer=None, use_ema=False):
@@ -62,8 +79,11 @@ def load(path, net, trainer=None, use_ema=False):
 
     A trainer that keeps a moving average gets "ema/<name>" and the update word back; from a file without any "ema/" key (a run
     that kept none) the average is seeded with the loaded weights and the word with step_count, said once on stderr.  A trainer
-    that keeps none ignores the keys.  use_ema=True (trainer=None): the net is given the AVERAGES instead of the raw weights, for
-    inference; a file without them raises a ValueError."""
+    that keeps none ignores the keys.  A trainer that accumulates gradients (accumulate_steps A > 1) gets "accum/<name>" and the
+    micro-step word back when the file was written with the same A; from any other file (no "accum/" key, or another accum_steps)
+    it starts a fresh cycle -- phase 0, the sum cleared -- said once on stderr.  A trainer with A = 1 ignores the keys.
+    use_ema=True (trainer=None): the net is given the AVERAGES instead of the raw weights, for inference; a file without them
+    raises a ValueError."""
     with safe_open(path, framework="pt") as f:
         meta = f.metadata() or {}
         keys = set(f.keys())
@@ -86,7 +106,10 @@ def load(path, net, trainer=None, use_ema=False):
                 raise ValueError("checkpoint %s holds no moving average of the weights (no 'ema/' tensors): it was written "
                                  "without --ema-decay" % path)
         want_ema = trainer is not None and getattr(trainer.opt, "ema", None) is not None
-        prefixes = ["ema/" if use_ema else "model/"] + (["ema/"] if want_ema and has_ema else [])
+        want_acc = trainer is not None and getattr(trainer.opt, "acc", None) is not None
+        has_acc = (want_acc and any(k.startswith("accum/") for k in keys) and "accum_micro" in meta
+                   and int(meta.get("accum_steps", 1)) == trainer.opt.accumulate_steps)
+        prefixes = ["ema/" if use_ema else "model/"] + (["ema/"] if want_ema and has_ema else []) + (["accum/"] if has_acc else [])
         for k, p in net.named_parameters():
             for pre in prefixes:
                 if pre + k not in keys:
@@ -135,6 +158,22 @@ def load(path, net, trainer=None, use_ema=False):
                         _seeded_note[0] = True
                         print("[checkpoint] %s holds no moving average of the weights: it starts from the loaded weights, at update %d"
                               % (path, int(meta.get("step_count", 0))), file=sys.stderr, flush=True)
+            if want_acc:
+                opt = trainer.opt
+                if has_acc:
+                    names = {id(p): k for k, p in net.named_parameters()}
+                    for p, (off, size) in zip(trainer.arena.params, trainer.arena.offsets):
+                        opt.acc[off:off + size].copy_(get("accum/" + names[id(p)], p).reshape(-1).to(opt.acc.device))
+                    opt.set_accum_micro(int(meta["accum_micro"]))
+                else:
+                    # written without accumulation, or with another accumulate_steps: its partial sum (if any) means nothing here
+                    opt.acc.zero_()
+                    opt.set_accum_micro(0)
+                    if not _fresh_cycle_note[0]:
+                        _fresh_cycle_note[0] = True
+                        print("[checkpoint] %s holds no gradient sum for accumulate_steps %d (written with %s): the accumulation "
+                              "starts a fresh cycle, at phase 0" % (path, opt.accumulate_steps, meta.get("accum_steps", "1")),
+                              file=sys.stderr, flush=True)
     import ops_f16
     ops_f16.weights_changed()
     return int(meta.get("step", 0))

@@ -46,14 +46,21 @@ __global__ void norm_reg_finalize_kernel(const double* __restrict__ partial, int
 // weights BEFORE the update, as rn_grad_norm_l2reg does -- into partial[block] (no clipping then: the norm is not an input)
 // EMA: the pass also keeps the exponential moving average of the weights (tf.train.ExponentialMovingAverage): with w' the
 // weight this launch stores and om = ema_dev[1] = 1 - d(n), what rn_ema_decay_eval left on the device, e <- e - (e - w') * om.
-// The trailing two arguments are not read by the EMA = false instantiations.
-template <int KIND, bool NORM, bool EMA>
+// The two EMA arguments are not read by the EMA = false instantiations.
+// ACC (rn_optimizer_step_accum): the pass sums the gradients of A launches in `acc` and applies their mean on the A-th.  Every wave
+// reads accum_dev = [p, applying], what rn_accum_phase_eval left on the device, once (a uniform load, like lr_dev[1]) and runs ONE
+// of three loops: p == 0 and not applying, acc = g * gs (acc is not read); 0 < p and not applying, acc += g * gs; applying, the
+// update from G = (acc + g * gs) * inv_accum in the place of g * gs (acc is not written: the next cycle's first launch overwrites
+// it).  The two accumulating loops touch nothing but acc and leave the block's `partial` pair as the last update wrote it; the
+// dropout counter advances in every launch.  The trailing three arguments are not read by the ACC = false instantiations.
+template <int KIND, bool NORM, bool EMA, bool ACC>
 __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                      float* __restrict__ s1, float* __restrict__ s2,
                                                      const float* __restrict__ wd, int64_t count, float lr, float gs,
                                                      float clip, const float* __restrict__ norm_sq, unsigned long long* advance, unsigned long long advance_by,
                                                      double* __restrict__ partial, const float* __restrict__ lr_dev,
-                                                     float* __restrict__ ema, const float* __restrict__ ema_dev) {
+                                                     float* __restrict__ ema, const float* __restrict__ ema_dev,
+                                                     float* __restrict__ acc, float inv_accum, const int* __restrict__ accum_dev) {
   __shared__ double red[2][T / 64];
   double n2 = 0.0, rg = 0.0;
   if (lr_dev) lr = lr_dev[1];  // the rate rn_lr_schedule_eval left on the device: one uniform load per wave, ahead of the loop
@@ -66,10 +73,34 @@ __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, cons
     cs = clip / fmaxf(gn, clip);
   }
   const int64_t nquad = count / 4;
+  if (ACC) {
+    const int phase = accum_dev[0];
+    if (accum_dev[1] == 0) {  // not the cycle's last launch: the sum only
+      if (phase == 0) {
+        for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < nquad; i += (int64_t)gridDim.x * T) {
+          const float4 gv = *reinterpret_cast<const float4*>(g + i * 4);
+          *reinterpret_cast<float4*>(acc + i * 4) = make_float4(gv.x * gs, gv.y * gs, gv.z * gs, gv.w * gs);
+        }
+      } else {
+        for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < nquad; i += (int64_t)gridDim.x * T) {
+          const float4 gv = *reinterpret_cast<const float4*>(g + i * 4);
+          const float4 cv = *reinterpret_cast<const float4*>(acc + i * 4);
+          *reinterpret_cast<float4*>(acc + i * 4) = make_float4(cv.x + gv.x * gs, cv.y + gv.y * gs, cv.z + gv.z * gs, cv.w + gv.w * gs);
+        }
+      }
+      return;
+    }
+  }
+  const float sc = ACC ? 1.f : gs;  // applying an accumulated gradient: G below carries the scale already
   for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < nquad; i += (int64_t)gridDim.x * T) {
     const float d = wd[(i * 4) / RN_OPT_BLOCK];
     float4 wv = *reinterpret_cast<float4*>(w + i * 4);
-    const float4 gv = *reinterpret_cast<const float4*>(g + i * 4);
+    float4 gv = *reinterpret_cast<const float4*>(g + i * 4);
+    if (ACC) {  // G, the mean of the cycle's gradients, stands where g * gs stood
+      const float4 cv = *reinterpret_cast<const float4*>(acc + i * 4);
+      gv.x = (cv.x + gv.x * gs) * inv_accum; gv.y = (cv.y + gv.y * gs) * inv_accum;
+      gv.z = (cv.z + gv.z * gs) * inv_accum; gv.w = (cv.w + gv.w * gs) * inv_accum;
+    }
     float4 av = *reinterpret_cast<float4*>(s1 + i * 4);
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (KIND != RN_OPT_MOMENTUM) bv = *reinterpret_cast<float4*>(s2 + i * 4);
@@ -77,13 +108,13 @@ __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, cons
     if (EMA) ev = *reinterpret_cast<float4*>(ema + i * 4);
     float* wp = &wv.x; const float* gp = &gv.x; float* ap = &av.x; float* bp = &bv.x; float* ep = &ev.x;
     if (NORM) {
-      const float t0 = gv.x * gs + d * wv.x, t1 = gv.y * gs + d * wv.y, t2 = gv.z * gs + d * wv.z, t3 = gv.w * gs + d * wv.w;
+      const float t0 = gv.x * sc + d * wv.x, t1 = gv.y * sc + d * wv.y, t2 = gv.z * sc + d * wv.z, t3 = gv.w * sc + d * wv.w;
       n2 += (double)(t0 * t0 + t1 * t1 + t2 * t2 + t3 * t3);
       rg += (double)(0.5f * d * (wv.x * wv.x + wv.y * wv.y + wv.z * wv.z + wv.w * wv.w));
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float gg = (gp[j] * gs + d * wp[j]) * cs;
+      const float gg = (gp[j] * sc + d * wp[j]) * cs;
       if (KIND == RN_OPT_MOMENTUM) {
         ap[j] = 0.9f * ap[j] + gg;
         wp[j] -= lr * ap[j];
@@ -145,9 +176,11 @@ extern "C" int rn_grad_norm_l2reg(const float* w, const float* grad, const float
 namespace {
 // lr_dev (optional): the kernel reads its rate from lr_dev[1] -- bias correction included -- and `lr` / `step` are not used
 // ema + ema_dev (optional, both or neither): the EMA instantiations, which also keep the moving average of the weights
+// acc + accum_dev (optional, both or neither; with `partial`): the ACC instantiations, which apply the mean of 1 / inv_accum gradients
 int launch_opt(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block, int64_t count, float lr,
                float grad_scale, float clip_norm, const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
-               double* partial, hipStream_t st, const float* lr_dev = nullptr, float* ema = nullptr, const float* ema_dev = nullptr) {
+               double* partial, hipStream_t st, const float* lr_dev = nullptr, float* ema = nullptr, const float* ema_dev = nullptr,
+               float* acc = nullptr, float inv_accum = 1.f, const int32_t* accum_dev = nullptr) {
   RN_CHECK_ARG(w && grad && state1 && wd_per_block, "optimizer: null pointer");
   RN_CHECK_ARG(count > 0 && count % RN_OPT_BLOCK == 0, "optimizer: count %lld not a multiple of %d", (long long)count,
                RN_OPT_BLOCK);
@@ -164,13 +197,15 @@ int launch_opt(int kind, float* w, const float* grad, float* state1, float* stat
   }
 #define RN_OPT_ARGS                                                                                                            \
   w, grad, state1, state2, wd_per_block, count, lr_eff, grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter,      \
-      (unsigned long long)advance_by, partial, lr_dev, ema, ema_dev
+      (unsigned long long)advance_by, partial, lr_dev, ema, ema_dev, acc, inv_accum, (const int*)accum_dev
 #define RN_OPT_LAUNCH(KIND_)                                                                                                    \
   do {                                                                                                                          \
-    if (ema && partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);        \
-    else if (ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);             \
-    else if (partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);         \
-    else hipLaunchKernelGGL((opt_step_kernel<KIND_, false, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);                     \
+    if (acc && ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);      \
+    else if (acc) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);       \
+    else if (ema && partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
+    else if (ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);      \
+    else if (partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);  \
+    else hipLaunchKernelGGL((opt_step_kernel<KIND_, false, false, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);              \
   } while (0)
   if (kind == RN_OPT_MOMENTUM) RN_OPT_LAUNCH(RN_OPT_MOMENTUM);
   else if (kind == RN_OPT_RMSPROP) RN_OPT_LAUNCH(RN_OPT_RMSPROP);
@@ -219,9 +254,23 @@ extern "C" int rn_optimizer_step_ema(int kind, float* w, const float* grad, floa
                     advance_by, partial, (hipStream_t)stream, lr_dev, ema, ema_dev);
 }
 
+extern "C" int rn_optimizer_step_accum(int kind, float* w, const float* grad, float* acc, float* state1, float* state2,
+                                       const float* wd_per_block, int64_t count, float lr, const float* lr_dev, float grad_scale,
+                                       float inv_accum, const int32_t* accum_dev, int64_t step, uint64_t* advance_counter,
+                                       uint64_t advance_by, double* partial, float* ema, const float* ema_dev, rn_stream_t stream) {
+  RN_CHECK_ARG(acc && accum_dev, "optimizer step + accumulation: null acc / accum_dev");
+  RN_CHECK_ARG(((uintptr_t)acc & 15) == 0, "optimizer step + accumulation: acc is not 16-byte aligned");
+  RN_CHECK_ARG(partial, "optimizer step + accumulation: null partial buffer (the fused-norm path only)");
+  RN_CHECK_ARG((ema != nullptr) == (ema_dev != nullptr), "optimizer step + accumulation: ema and ema_dev go together");
+  RN_CHECK_ARG(!ema || ((uintptr_t)ema & 15) == 0, "optimizer step + accumulation: ema is not 16-byte aligned");
+  RN_CHECK_ARG(inv_accum > 0.f && inv_accum <= 1.f, "optimizer step + accumulation: inv_accum %g outside (0, 1]", (double)inv_accum);
+  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, 0.f, nullptr, step, advance_counter, advance_by,
+                    partial, (hipStream_t)stream, lr_dev, ema, ema_dev, acc, inv_accum, accum_dev);
+}
+
 namespace {
 // d(n) of rn_ema_decay_eval (include/rn_hip.h) and its complement, each formed in double and rounded to float once
-__global__ void ema_decay_eval_kernel(double decay, int warmup, unsigned long long* num_updates_dev, float* ema_dev) {
+__device__ void ema_decay_eval(double decay, int warmup, unsigned long long* num_updates_dev, float* ema_dev) {
   const unsigned long long n = *num_updates_dev;
   double d = decay;
   if (warmup) d = fmin(decay, (1.0 + (double)n) / (10.0 + (double)n));
@@ -229,13 +278,38 @@ __global__ void ema_decay_eval_kernel(double decay, int warmup, unsigned long lo
   ema_dev[1] = (float)(1.0 - d);
   *num_updates_dev = n + 1;
 }
+
+__global__ void ema_decay_eval_kernel(double decay, int warmup, unsigned long long* num_updates_dev, float* ema_dev) {
+  ema_decay_eval(decay, warmup, num_updates_dev, ema_dev);
+}
+
+// gated (gradient accumulation): only the launch that applies an update -- accum_dev[1] != 0 -- advances the average's word
+__global__ void ema_decay_eval_gated_kernel(double decay, int warmup, unsigned long long* num_updates_dev, float* ema_dev,
+                                            const int* accum_dev) {
+  if (accum_dev[1] != 0) ema_decay_eval(decay, warmup, num_updates_dev, ema_dev);
+}
+
+int check_ema_decay_eval(double decay, const uint64_t* num_updates_dev, const float* ema_dev) {
+  RN_CHECK_ARG(num_updates_dev && ema_dev, "ema_decay_eval: null pointer");
+  RN_CHECK_ARG(decay > 0.0 && decay < 1.0, "ema_decay_eval: decay %g outside (0, 1)", decay);
+  return RN_OK;
+}
 }  // namespace
 
 extern "C" int rn_ema_decay_eval(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, rn_stream_t stream) {
-  RN_CHECK_ARG(num_updates_dev && ema_dev, "ema_decay_eval: null pointer");
-  RN_CHECK_ARG(decay > 0.0 && decay < 1.0, "ema_decay_eval: decay %g outside (0, 1)", decay);
+  if (int rc = check_ema_decay_eval(decay, num_updates_dev, ema_dev)) return rc;
   hipLaunchKernelGGL(ema_decay_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, decay, warmup, (unsigned long long*)num_updates_dev,
                      ema_dev);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
+}
+
+extern "C" int rn_ema_decay_eval_gated(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, const int32_t* accum_dev,
+                                       rn_stream_t stream) {
+  if (int rc = check_ema_decay_eval(decay, num_updates_dev, ema_dev)) return rc;
+  RN_CHECK_ARG(accum_dev, "ema_decay_eval_gated: null accum_dev");
+  hipLaunchKernelGGL(ema_decay_eval_gated_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, decay, warmup,
+                     (unsigned long long*)num_updates_dev, ema_dev, (const int*)accum_dev);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }
@@ -258,7 +332,7 @@ __device__ double lr_schedule_value(const rn_lr_schedule& d, uint64_t s) {
   return base;
 }
 
-__global__ void lr_schedule_eval_kernel(rn_lr_schedule d, unsigned long long* step_dev, float* lr_dev, int opt_kind) {
+__device__ void lr_schedule_eval(const rn_lr_schedule& d, unsigned long long* step_dev, float* lr_dev, int opt_kind) {
   const unsigned long long s = *step_dev;
   const float lr = (float)lr_schedule_value(d, (uint64_t)s);
   float eff = lr;
@@ -270,9 +344,18 @@ __global__ void lr_schedule_eval_kernel(rn_lr_schedule d, unsigned long long* st
   lr_dev[1] = eff;
   *step_dev = s + 1;
 }
-}  // namespace
 
-extern "C" int rn_lr_schedule_eval(rn_lr_schedule d, uint64_t* step_dev, float* lr_dev, int optimizer_kind, rn_stream_t stream) {
+__global__ void lr_schedule_eval_kernel(rn_lr_schedule d, unsigned long long* step_dev, float* lr_dev, int opt_kind) {
+  lr_schedule_eval(d, step_dev, lr_dev, opt_kind);
+}
+
+// gated (gradient accumulation): only the launch that applies an update -- accum_dev[1] != 0 -- evaluates and advances the schedule
+__global__ void lr_schedule_eval_gated_kernel(rn_lr_schedule d, unsigned long long* step_dev, float* lr_dev, int opt_kind,
+                                              const int* accum_dev) {
+  if (accum_dev[1] != 0) lr_schedule_eval(d, step_dev, lr_dev, opt_kind);
+}
+
+int check_lr_schedule_eval(const rn_lr_schedule& d, const uint64_t* step_dev, const float* lr_dev, int optimizer_kind) {
   RN_CHECK_ARG(step_dev && lr_dev, "lr_schedule_eval: null pointer");
   RN_CHECK_ARG(optimizer_kind == RN_OPT_MOMENTUM || optimizer_kind == RN_OPT_RMSPROP || optimizer_kind == RN_OPT_ADAM,
                "lr_schedule_eval: unknown optimizer kind %d", optimizer_kind);
@@ -287,7 +370,43 @@ extern "C" int rn_lr_schedule_eval(rn_lr_schedule d, uint64_t* step_dev, float* 
                  "lr_schedule_eval: boundaries must be non-negative and strictly increasing (entry %d)", i);
   RN_CHECK_ARG(d.total_steps > d.warmup_steps || (d.kind != RN_LR_COSINE && d.total_steps == 0),
                "lr_schedule_eval: total_steps %lld is not above warmup_steps %lld", (long long)d.total_steps, (long long)d.warmup_steps);
+  return RN_OK;
+}
+}  // namespace
+
+extern "C" int rn_lr_schedule_eval(rn_lr_schedule d, uint64_t* step_dev, float* lr_dev, int optimizer_kind, rn_stream_t stream) {
+  if (int rc = check_lr_schedule_eval(d, step_dev, lr_dev, optimizer_kind)) return rc;
   hipLaunchKernelGGL(lr_schedule_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d, (unsigned long long*)step_dev, lr_dev, optimizer_kind);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
+}
+
+extern "C" int rn_lr_schedule_eval_gated(rn_lr_schedule d, uint64_t* step_dev, float* lr_dev, int optimizer_kind,
+                                         const int32_t* accum_dev, rn_stream_t stream) {
+  if (int rc = check_lr_schedule_eval(d, step_dev, lr_dev, optimizer_kind)) return rc;
+  RN_CHECK_ARG(accum_dev, "lr_schedule_eval_gated: null accum_dev");
+  hipLaunchKernelGGL(lr_schedule_eval_gated_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d, (unsigned long long*)step_dev, lr_dev,
+                     optimizer_kind, (const int*)accum_dev);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
+}
+
+namespace {
+// p = micro-steps seen so far mod A: accum_dev = [p, p == A - 1] for this launch's kernels, and the word advances
+__global__ void accum_phase_eval_kernel(int accumulate_steps, unsigned long long* micro_dev, int* accum_dev) {
+  const unsigned long long m = *micro_dev;
+  const int p = (int)(m % (unsigned long long)accumulate_steps);
+  accum_dev[0] = p;
+  accum_dev[1] = (p == accumulate_steps - 1) ? 1 : 0;
+  *micro_dev = m + 1;
+}
+}  // namespace
+
+extern "C" int rn_accum_phase_eval(int32_t accumulate_steps, uint64_t* micro_dev, int32_t* accum_dev, rn_stream_t stream) {
+  RN_CHECK_ARG(micro_dev && accum_dev, "accum_phase_eval: null pointer");
+  RN_CHECK_ARG(accumulate_steps >= 1, "accum_phase_eval: accumulate_steps %d < 1", (int)accumulate_steps);
+  hipLaunchKernelGGL(accum_phase_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int)accumulate_steps,
+                     (unsigned long long*)micro_dev, (int*)accum_dev);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }

@@ -171,14 +171,34 @@ class Optimizer(object):
     tf.train.ExponentialMovingAverage's semantics, kept by the update kernel itself -- with n = updates applied before this one and
     w' the weight after it, e <- e - (e - w') * (1 - d(n)), d(n) = min(D, (1 + n) / (10 + n)) (`ema_warmup`) or D.  n is the
     average's own device word `ema_updates_dev`: begin_step launches rn_ema_decay_eval, which leaves [d(n), 1 - d(n)] in `ema_dev`
-    and advances the word, so this too adds no launch argument that changes from step to step."""
+    and advances the word, so this too adds no launch argument that changes from step to step.
+
+    `accumulate_steps` A (an integer >= 1, default 1; A > 1: device arena, no clipping): gradient accumulation.  A call of step()
+    is a MICRO-step; an update is applied on every A-th one, from the mean of the last A gradients (each already times grad_scale).
+    The backward kernels overwrite a parameter's gradient slot, so the sum lives in an arena of its own, `acc` (+4 B per parameter),
+    kept by the update kernel: begin_step launches rn_accum_phase_eval, which leaves [p, p == A - 1] in `accum_dev` from the device
+    word `micro_dev` (p = micro-steps so far mod A) and advances the word; rn_optimizer_step_accum reads the pair and either only
+    sums (acc = g or acc += g: 8 / 12 B per element, nothing else touched) or applies (acc + g) / A (+4 B per element over the plain
+    update).  The schedule's and the average's one-thread kernels run behind the same gate, so `step_count`, `step_dev`,
+    `ema_updates_dev`, Adam's bias correction and current_lr() all count UPDATES.  On a micro-step that only sums, `norm_reg` (and
+    regularization_loss) keep the last update's values.  The dropout counter advances every micro-step.  Again no launch argument
+    changes from one micro-step to the next: one captured graph serves every phase.  With A = 1 none of this is allocated or launched."""
 
     def __init__(self, arena, kind='momentum', learning_rate=1e-2, grad_clip_norm=None, schedule=None, ema_decay=None,
-                 ema_warmup=True):
+                 ema_warmup=True, accumulate_steps=1):
         assert kind in ['momentum', 'adam', 'rmsprop']
         self.arena, self.kind, self.lr = arena, kind, float(learning_rate)
         self.clip = float(grad_clip_norm) if grad_clip_norm is not None else 0.0
         dev = arena.weights.device
+        if isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, (int, np.integer)) or accumulate_steps < 1:
+            raise ValueError("accumulate_steps %r is not an integer >= 1" % (accumulate_steps,))
+        self.accumulate_steps = int(accumulate_steps)
+        if self.accumulate_steps > 1 and self.clip > 0.0:
+            raise ValueError("accumulate_steps > 1 with grad_clip_norm: the clipped update takes the norm as an input, and clipping "
+                             "an accumulated gradient is not implemented")
+        if self.accumulate_steps > 1 and (dev.type != 'cuda' or not FUSED_OPT_NORM):
+            raise _rn.RnError("gradient accumulation is kept by the device's fused update kernel: it needs a device arena and "
+                              "RN_FUSED_OPT_NORM=1")
         self.schedule = schedule
         if schedule is not None:
             assert isinstance(schedule, LRSchedule)
@@ -210,7 +230,26 @@ class Optimizer(object):
         if dev.type == 'cuda':
             n = 4 * int(_rn.lib().rn_optimizer_norm_pairs(arena.count)) + 16
             self._partial = torch.zeros(2 * n, dtype=torch.float64, device=dev)
+        # the sum of a cycle's gradients and the two device words of its phase: HERE as well, for the same reason
+        self.acc = self.micro_dev = self.accum_dev = None
+        self._phase = 0                 # the host's mirror of micro_dev % A: micro-steps of the current cycle already summed
+        if self.accumulate_steps > 1:
+            self.acc = torch.zeros_like(arena.weights)
+            self.micro_dev = torch.zeros(1, dtype=torch.int64, device=dev)          # (the kernel's uint64: same bits)
+            self.accum_dev = torch.zeros(2, dtype=torch.int32, device=dev)
         self.step_count = 0
+
+    def count_step(self):
+        """The host's side of one (micro-)step: step_count counts UPDATES, so with accumulate_steps = A it moves on every A-th call.
+        Returns whether this call's step applies an update.  begin_step calls it; a replayed graph's owner calls it per replay."""
+        if self.acc is None:
+            self.step_count += 1
+            return True
+        applying = self._phase == self.accumulate_steps - 1
+        self._phase = (self._phase + 1) % self.accumulate_steps
+        if applying:
+            self.step_count += 1
+        return applying
 
     def step(self, grad_scale=1.0, advance_counter=None):
         """`advance_counter`: the device word the dropout masks hash; bumped by the optimizer kernel itself."""
@@ -253,9 +292,14 @@ class Optimizer(object):
     # -- the update in slices of the arena (no clipping): Trainer.step updates the heads + FPN slice on a side stream while the
     # backbone's backward pass still runs, the rest after it; every slice's launch leaves its share of (sum g'^2, regulariser)
     def begin_step(self):
-        self.step_count += 1
+        applying = self.count_step()
+        # (the update this micro-step's cycle ends in, 1-based: Adam's bias correction where the rate is a launch argument)
+        self._update_no = self.step_count if applying else self.step_count + 1
         self._pairs = 0
         assert self._partial is not None, "the fused norm path needs a device arena"
+        if self.acc is not None:
+            self._begin_accum_step()
+            return
         if self.lr_dev is not None:
             # this update's rate, on the main stream ahead of every slice; the kernel advances step_dev itself
             _rn.check(_rn.lib().rn_lr_schedule_eval(self._sched_struct, self.step_dev.data_ptr(), _rn.f32(self.lr_dev),
@@ -268,6 +312,21 @@ class Optimizer(object):
             self._sched_event = torch.cuda.Event()       # one event behind both one-thread kernels
             self._sched_event.record()
 
+    def _begin_accum_step(self):
+        """begin_step with accumulate_steps > 1: the phase first, then the schedule's and the average's kernels behind its gate (they
+        do nothing on a micro-step that only sums), and ONE event behind all three -- a slice on a side stream reads accum_dev too."""
+        L_ = _rn.lib()
+        _rn.check(L_.rn_accum_phase_eval(self.accumulate_steps, self.micro_dev.data_ptr(), self.accum_dev.data_ptr(), _rn.stream()),
+                  'rn_accum_phase_eval')
+        if self.lr_dev is not None:
+            _rn.check(L_.rn_lr_schedule_eval_gated(self._sched_struct, self.step_dev.data_ptr(), _rn.f32(self.lr_dev), _rn.OPT[self.kind],
+                                                   self.accum_dev.data_ptr(), _rn.stream()), 'rn_lr_schedule_eval_gated')
+        if self.ema is not None:
+            _rn.check(L_.rn_ema_decay_eval_gated(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(),
+                                                 _rn.f32(self.ema_dev), self.accum_dev.data_ptr(), _rn.stream()), 'rn_ema_decay_eval_gated')
+        self._sched_event = torch.cuda.Event()
+        self._sched_event.record()
+
     def step_slice(self, lo, hi, grad_scale, advance_counter=None, stream=None):
         a, L_ = self.arena, _rn.lib()
         assert 0 <= lo < hi <= a.count and lo % OPT_BLOCK == 0 and hi % OPT_BLOCK == 0
@@ -275,11 +334,24 @@ class Optimizer(object):
         assert 2 * (self._pairs + npairs) <= self._partial.numel()
         part = self._partial[2 * self._pairs:]
         self._pairs += npairs
-        if (self.lr_dev is not None or self.ema is not None) and stream is not None:
-            # a slice on another stream reads lr_dev / ema_dev too: behind the one-thread kernels, not the whole main stream
+        if (self.lr_dev is not None or self.ema is not None or self.acc is not None) and stream is not None:
+            # a slice on another stream reads lr_dev / ema_dev / accum_dev too: behind the one-thread kernels, not the whole main stream
             other = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(getattr(stream, 'value', stream)))
             other.wait_event(self._sched_event)
             stream = ctypes.c_void_p(other.cuda_stream)
+        if self.acc is not None:
+            _rn.check(L_.rn_optimizer_step_accum(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(),
+                                                 self.acc[lo:].data_ptr(), self.state1[lo:].data_ptr(),
+                                                 self.state2[lo:].data_ptr() if self.state2 is not None else None,
+                                                 a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), hi - lo, self.lr,
+                                                 _rn.f32(self.lr_dev) if self.lr_dev is not None else None, grad_scale,
+                                                 1.0 / self.accumulate_steps, self.accum_dev.data_ptr(), self._update_no,
+                                                 advance_counter.data_ptr() if advance_counter is not None else None,
+                                                 ops.DROPOUT_COUNTER_STEP, part.data_ptr(),
+                                                 self.ema[lo:].data_ptr() if self.ema is not None else None,
+                                                 _rn.f32(self.ema_dev) if self.ema is not None else None,
+                                                 stream if stream is not None else _rn.stream()), 'rn_optimizer_step_accum')
+            return
         if self.ema is not None:
             _rn.check(L_.rn_optimizer_step_ema(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(),
                                                self.state1[lo:].data_ptr(),
@@ -322,6 +394,12 @@ class Optimizer(object):
             self.step_dev.fill_(self.step_count)
         if self.ema_updates_dev is not None:
             self.ema_updates_dev.fill_(self.step_count)
+
+    def set_accum_micro(self, n):
+        """Micro-steps taken so far (a restored checkpoint): the device word rn_accum_phase_eval reads and the host's phase."""
+        if self.acc is not None:
+            self.micro_dev.fill_(int(n))
+            self._phase = int(n) % self.accumulate_steps
 
     def ema_decay_value(self, n):
         """d(n), the decay of the update that follows n applied ones, in float64: the host's copy of what rn_ema_decay_eval forms."""
@@ -459,7 +537,7 @@ class Trainer(object):
                  loss_mode='bce_dice', device='cuda', use_graph=False, process_group=None,
                  direct_param_grads=True, wgrad_side_stream=False, defer_reductions=True, overlap=True,
                  force_collective=False, input_fn=None, check_interval=50, capture_collectives=None, lr_schedule=None,
-                 ema_decay=None, ema_warmup=True):
+                 ema_decay=None, ema_warmup=True, accumulate_steps=1):
         self.net, self.levels = net, levels or build_levels()
         self.device = torch.device(device)
         if self.device.type == 'cuda':
@@ -477,8 +555,12 @@ class Trainer(object):
         # ema_decay: the update kernel also keeps a moving average of the weights (Optimizer docstring; ema_weights() runs the net
         # on it).  Its decay is read from the device like a scheduled rate: no host scalar, so nothing about the one-graph step or
         # its cache key changes
+        # accumulate_steps A: step() is a micro-step, every A-th one applies the mean of the last A gradients (Optimizer docstring).
+        # Phase and gate live on the device as well: the step stays ONE graph, captured once and replayed for every phase; A is part
+        # of its cache key.  With several ranks every micro-step's gradient is all-reduced (1 / world applied as it is summed)
         ema_kw = {} if ema_decay is None else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}
-        self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule, **ema_kw)
+        self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule,
+                             accumulate_steps=accumulate_steps, **ema_kw)
         self.allreduce = GradientAllReduce(self.arena, process_group, force=force_collective)
         self.use_graph = use_graph
         self.input_fn = input_fn       # optional: features = input_fn(), run INSIDE segment A (e.g. device-side label assignment)
@@ -903,10 +985,10 @@ class Trainer(object):
         self._static = _clone_tree(features)
         self._warm_up()
         g = torch.cuda.CUDAGraph()
-        count = self.opt.step_count
+        count, phase = self.opt.step_count, self.opt._phase
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
             self._graph_out = self._run_step(self._static)
-        self.opt.step_count = count                 # (recorded, not run: replays count their own steps)
+        self.opt.step_count, self.opt._phase = count, phase      # (recorded, not run: replays count their own steps)
         ranges = [r for r in self.schedule if r[1] <= self.cut_offset]
         # (the parts' arena ranges are kept for reporting; no graph per part)
         self._graphs = (g, [], ranges, self._graph_out, self._static, True, list(self.schedule))
@@ -931,7 +1013,7 @@ class Trainer(object):
             if self._lr_changes > 3:
                 whole = False
         if whole:
-            key = (key, 'whole', self.opt.schedule if scheduled else self.opt.lr, id(self.allreduce))
+            key = (key, 'whole', self.opt.schedule if scheduled else self.opt.lr, id(self.allreduce), self.opt.accumulate_steps)
         if self.use_graph:
             if self._graphs is None:
                 self._graph_cache.clear()
@@ -959,7 +1041,7 @@ class Trainer(object):
             if self._graphs[5]:
                 # the whole step was that one replay: what is left is the update's host-side bookkeeping
                 self.schedule[:] = self._graphs[6]
-                self.opt.step_count += 1
+                self.opt.count_step()               # (updates, not replays: every accumulate_steps-th replay applied one)
                 import ops_f16
                 ops_f16.weights_changed()
             else:
@@ -1170,13 +1252,16 @@ def build_parser():
                         help='rate after the warm-up: constant | step (x --lr-decay-factor at every --lr-decay-steps) | cosine '
                              '(down to --lr-final-factor x the rate at --lr-total-steps)')
     parser.add_argument('--lr-warmup-steps', type=int, default=None, metavar='N',
-                        help='linear warm-up from --lr-warmup-factor x the rate to the rate over the first N updates (default 0)')
+                        help='linear warm-up from --lr-warmup-factor x the rate to the rate over the first N updates (default 0; '
+                             'updates, not steps, with --accumulate-steps)')
     parser.add_argument('--lr-warmup-factor', type=float, default=None, metavar='F', help='default 1/3')
     parser.add_argument('--lr-decay-steps', type=int, nargs='+', default=None, metavar='A',
                         help='with --lr-schedule step: update counts (at most %d, increasing) at which the rate drops' % LRSchedule.MAX_BOUNDARIES)
     parser.add_argument('--lr-decay-factor', type=float, default=None, metavar='G', help='default 0.1')
     parser.add_argument('--lr-total-steps', type=int, default=None, metavar='T',
-                        help='update count at which the cosine reaches its floor (default: restored step + epochs x steps per epoch)')
+                        help='update count at which the cosine reaches its floor (default: the update count the run ends at: restored '
+                             'step + epochs x steps per epoch; with --accumulate-steps A the updates restored + (steps into the '
+                             'restored cycle + epochs x steps per epoch) // A)')
     parser.add_argument('--lr-final-factor', type=float, default=None, metavar='F', help='default 0')
     # moving average of the weights (Optimizer docstring); without --ema-decay: none, as before
     parser.add_argument('--ema-decay', type=float, default=None, metavar='D',
@@ -1184,7 +1269,21 @@ def build_parser():
                              'stored in the checkpoint and evaluated beside the raw weights')
     parser.add_argument('--ema-no-warmup', action='store_true',
                         help='with --ema-decay: the decay is D from the first update on instead of min(D, (1 + n) / (10 + n))')
+    # gradient accumulation (Optimizer docstring); without --accumulate-steps: an update per step, as before
+    parser.add_argument('--accumulate-steps', type=int, default=1, metavar='A',
+                        help='apply an update on every A-th step, from the mean of the last A gradients (1 <= A <= 64, default 1: an '
+                             'effective batch A times larger at +4 B per parameter); not with --grad-clip-norm.  --lr-warmup-steps, '
+                             '--lr-decay-steps and --lr-total-steps then count UPDATES, not steps')
     return parser
+
+
+def accumulate_flag_error(args):
+    """What is wrong with --accumulate-steps as given (checked before any dataset or device is touched), or None."""
+    if not 1 <= args.accumulate_steps <= 64:
+        return '--accumulate-steps A: 1 <= A <= 64 (got %d)' % args.accumulate_steps
+    if args.accumulate_steps > 1 and args.grad_clip_norm is not None:
+        return '--accumulate-steps with --grad-clip-norm: clipping an accumulated gradient is not implemented'
+    return None
 
 
 def ema_flag_error(args):
@@ -1218,17 +1317,20 @@ def lr_flag_error(args):
     return None
 
 
-def schedule_from_args(args, steps_per_epoch, restored_step):
+def schedule_from_args(args, steps_per_epoch, restored_step, phase=0):
     """The LRSchedule the --lr-* flags describe, or None when none of them is given (the constant-rate path, unchanged).  Pure:
-    no device, no files.  --lr-total-steps defaults to the update count this run ends at.  Raises ValueError (main: parser.error)
-    for combinations that make no sense."""
+    no device, no files.  --lr-total-steps defaults to the update count this run ends at: with --accumulate-steps A,
+    `restored_step` is the number of UPDATES restored and `phase` the micro-steps of the restored, unfinished cycle.  Raises
+    ValueError (main: parser.error) for combinations that make no sense."""
     if all(getattr(args, f) is None for f in LR_FLAGS):
         return None
     err = lr_flag_error(args)
     if err:
         raise ValueError(err)
     warmup = args.lr_warmup_steps or 0
-    total = args.lr_total_steps if args.lr_total_steps is not None else int(restored_step) + args.epochs * int(steps_per_epoch)
+    A = int(getattr(args, 'accumulate_steps', 1))
+    total = (args.lr_total_steps if args.lr_total_steps is not None
+             else int(restored_step) + (int(phase) + args.epochs * int(steps_per_epoch)) // A)
     if total <= warmup:
         raise ValueError('the run ends at update %d, not above --lr-warmup-steps %d (see --lr-total-steps)' % (total, warmup))
     return LRSchedule(kind=args.lr_schedule or 'constant', base_lr=args.learning_rate, warmup_steps=warmup,
@@ -1272,6 +1374,8 @@ def broadcast_initial_state(trainer, src=0):
             dist.broadcast(trainer.opt.state2, src=src)
         if trainer.opt.ema is not None:
             dist.broadcast(trainer.opt.ema, src=src)
+        if trainer.opt.acc is not None:
+            dist.broadcast(trainer.opt.acc, src=src)
 
 
 LAST_RUN = {}
@@ -1299,6 +1403,8 @@ def main(argv=None):
         parser.error(lr_flag_error(args))
     if ema_flag_error(args):
         parser.error(ema_flag_error(args))
+    if accumulate_flag_error(args):
+        parser.error(accumulate_flag_error(args))
     K = args.samples_per_step
     if K != 1 and not files:
         parser.error('--samples-per-step groups raw uint8 image files: it needs --dataset pascal ... or coco ...')
@@ -1361,14 +1467,19 @@ def main(argv=None):
     else:
         feed = dataset.DeviceFeed(loader, levels, scale=args.scale, device=dev)
     restored = checkpoint.saved_step(path) if (path is not None and os.path.exists(path)) else 0
+    A, phase = args.accumulate_steps, 0
+    if A > 1 and path is not None and os.path.exists(path):
+        # the schedule counts updates: those the file holds, and the run resumes `phase` micro-steps into a cycle
+        restored, phase = checkpoint.saved_updates(path, A)
     try:
-        lr_schedule = schedule_from_args(args, steps_per_epoch, restored)
+        lr_schedule = schedule_from_args(args, steps_per_epoch, restored, phase)
     except ValueError as e:
         parser.error(str(e))
     trainer = Trainer(net, levels, optimizer=args.optimizer, learning_rate=args.learning_rate,
                       grad_clip_norm=args.grad_clip_norm, loss_mode=args.loss, device=dev, use_graph=not args.no_graph,
                       input_fn=feed, **({'lr_schedule': lr_schedule} if lr_schedule is not None else {}),
-                      **({'ema_decay': args.ema_decay, 'ema_warmup': not args.ema_no_warmup} if args.ema_decay is not None else {}))
+                      **({'ema_decay': args.ema_decay, 'ema_warmup': not args.ema_no_warmup} if args.ema_decay is not None else {}),
+                      **({'accumulate_steps': A} if A > 1 else {}))
     step = 0
     if path is not None and os.path.exists(path):
         step = checkpoint.load(path, net, trainer)                                 # every rank reads the same file
@@ -1390,7 +1501,8 @@ def main(argv=None):
                 if step % 20 == 0 and rank == 0:
                     print('epoch %d step %d class_loss %.4f regr_loss %.4f reg %.4f lr %.3g' % (
                         epoch, step, out['class_loss'].item(), out['regr_loss'].item(), out['regularization_loss'].item(),
-                        trainer.opt.current_lr()), flush=True)                     # (the rate of the NEXT update: host-side, no sync)
+                        trainer.opt.current_lr())                                  # (the rate of the NEXT update: host-side, no sync)
+                          + (' update %d' % trainer.opt.step_count if A > 1 else ''), flush=True)
             trainer.check_device_errors()
             if args.augment and getattr(loader, 'skipped', 0) != skipped0:
                 raise _rn.RnError("the loader skipped samples while iterating: the augmentation's ordinals no longer equal the "
@@ -1402,7 +1514,7 @@ def main(argv=None):
         feed.close()
     # what the run did, for measuring tools (tools/files_bench.py): wall time of the training loop (captures, checkpoints included)
     LAST_RUN.update(steps=step, seconds=time.perf_counter() - t0, samples=feed.samples_staged, recaptures=trainer.recaptures,
-                    graph_sets=len(trainer._graph_cache))
+                    graph_sets=len(trainer._graph_cache), updates=trainer.opt.step_count)
     if args.eval_images and rank == 0:
         if args.eval_dataset:
             from data_loaders.inferred import Inferred
