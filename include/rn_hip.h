@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 413
+#define RN_API_VERSION 414
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -880,7 +880,8 @@ int rn_nms_classwise(const float* boxes, const float* scores, const int32_t* cla
  * + tf.clip_by_global_norm (train.py:111-134,221) on ONE flat fp32 parameter arena.
  * The arena is cut into blocks of RN_OPT_BLOCK elements; wd_per_block[b] is the L2 scale of
  * the parameter that owns block b (0 for gamma/beta/bias and padding).
- *   g' = grad*grad_scale*clip_scale + wd*w      (grad_scale = 1/world_size)
+ *   g' = (grad*grad_scale + wd*w) * clip_scale  (grad_scale = 1/world_size; clip_scale = clip/max(||grad*grad_scale + wd*w||, clip):
+ *                                                the norm includes the regulariser's gradient, as compute_gradients(loss) does)
  */
 #define RN_OPT_BLOCK 1024
 size_t rn_optimizer_workspace(int64_t count);
@@ -988,6 +989,24 @@ int rn_optimizer_step_accum(int kind, float* w, const float* grad, float* acc, f
                             const float* wd_per_block, int64_t count, float lr, const float* lr_dev, float grad_scale,
                             float inv_accum, const int32_t* accum_dev, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
                             double* partial, float* ema, const float* ema_dev, rn_stream_t stream);
+/* The CLIPPED update with nothing step-dependent among its launch arguments, so that it can be a node of a captured step like the
+ * unclipped entries: clip_scale = clip_norm / max(sqrt(norm_sq[0]), clip_norm) is formed by the kernel from the device scalar, the
+ * rate is lr_dev[1] -- bias correction included -- when lr_dev is given (`lr` / `step` are not read then, as in
+ * rn_optimizer_step_norm_lrdev), else `lr` exactly as rn_optimizer_step takes it (RN_OPT_ADAM then needs step >= 1, which DOES
+ * change from step to step); ema + ema_dev both or neither, as in rn_optimizer_step_ema.  No `partial`: the norm is an input of
+ * this pass, so the pass before it forms it (rn_grad_norm_partial + rn_norm_reg_finalize, or rn_grad_norm_l2reg).  Checked by the
+ * entry before any launch: clip_norm > 0, non-null norm_sq, ema / ema_dev together and ema 16-byte aligned, count whole blocks,
+ * state2 for RN_OPT_RMSPROP / RN_OPT_ADAM, step >= 1 for RN_OPT_ADAM without lr_dev. */
+int rn_optimizer_step_clip(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
+                           int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm, const float* norm_sq,
+                           int64_t step, uint64_t* advance_counter, uint64_t advance_by, float* ema, const float* ema_dev,
+                           rn_stream_t stream);
+/* The norm pass of rn_grad_norm_l2reg for a SLICE [w, w + count) of the arena (wd_per_block points at the slice's first block):
+ * rn_optimizer_norm_pairs(count) (double, double) pairs of (sum g'^2, L2 regulariser value) into `partial`, in the layout
+ * rn_optimizer_step_norm writes; rn_norm_reg_finalize over the pairs of all slices gives [sum g'^2, reg].  The caller owns
+ * `partial`: no workspace, nothing a capture may not contain. */
+int rn_grad_norm_partial(const float* w, const float* grad, const float* wd_per_block, int64_t count, float grad_scale,
+                         double* partial, rn_stream_t stream);
 /* *counter += inc on the stream (the same counter, for callers that run backward passes without an optimizer step) */
 int rn_counter_add(uint64_t* counter, uint64_t inc, rn_stream_t stream);
 /* p[0..count) = 0 (16-byte aligned): the gradient arena before a backward pass (the reference's graph zero-initialises

@@ -173,6 +173,18 @@ extern "C" int rn_grad_norm_l2reg(const float* w, const float* grad, const float
   return RN_OK;
 }
 
+extern "C" int rn_grad_norm_partial(const float* w, const float* grad, const float* wd_per_block, int64_t count, float grad_scale,
+                                    double* partial, rn_stream_t stream) {
+  RN_CHECK_ARG(w && grad && wd_per_block && partial, "grad_norm_partial: null pointer");
+  RN_CHECK_ARG(count > 0 && count % RN_OPT_BLOCK == 0, "grad_norm_partial: count %lld not a multiple of %d", (long long)count,
+               RN_OPT_BLOCK);
+  // grid_for's grid, not the NB-capped one of rn_grad_norm_l2reg: one pair per block = rn_optimizer_norm_pairs(count) pairs
+  hipLaunchKernelGGL(norm_reg_kernel, dim3(grid_for(count / 4)), dim3(T), 0, (hipStream_t)stream, w, grad, wd_per_block, count,
+                     grad_scale, partial);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
+}
+
 namespace {
 // lr_dev (optional): the kernel reads its rate from lr_dev[1] -- bias correction included -- and `lr` / `step` are not used
 // ema + ema_dev (optional, both or neither): the EMA instantiations, which also keep the moving average of the weights
@@ -252,6 +264,19 @@ extern "C" int rn_optimizer_step_ema(int kind, float* w, const float* grad, floa
   RN_CHECK_ARG(!(partial && clip_norm > 0.f), "optimizer step + ema: the fused norm (partial) is formed without clipping");
   return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter,
                     advance_by, partial, (hipStream_t)stream, lr_dev, ema, ema_dev);
+}
+
+extern "C" int rn_optimizer_step_clip(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
+                                      int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm,
+                                      const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by, float* ema,
+                                      const float* ema_dev, rn_stream_t stream) {
+  RN_CHECK_ARG(clip_norm > 0.f, "optimizer step + clip: clip_norm %g is not above 0", (double)clip_norm);
+  RN_CHECK_ARG(norm_sq, "optimizer step + clip: null norm_sq");
+  RN_CHECK_ARG((ema != nullptr) == (ema_dev != nullptr), "optimizer step + clip: ema and ema_dev go together");
+  RN_CHECK_ARG(!ema || ((uintptr_t)ema & 15) == 0, "optimizer step + clip: ema is not 16-byte aligned");
+  // no `partial`: the <KIND, false, EMA, false> instantiations (the norm is this update's INPUT, formed by the pass before it)
+  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter,
+                    advance_by, nullptr, (hipStream_t)stream, lr_dev, ema, ema_dev);
 }
 
 extern "C" int rn_optimizer_step_accum(int kind, float* w, const float* grad, float* acc, float* state1, float* state2,

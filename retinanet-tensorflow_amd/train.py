@@ -83,7 +83,7 @@ class LRSchedule(object):
                 cosine     base * (ff + (1 - ff) * 0.5 * (1 + cos(pi * min(1, (s - W) / (T - W)))))
 
     in float64, rounded to float32 once.  rn_lr_schedule_eval evaluates the same descriptor on the device (struct()), where a
-    replayed graph advances it by itself; value(s) is the host's copy of the formula (launch arguments of the clipping path,
+    replayed graph advances it by itself; value(s) is the host's copy of the formula (launch arguments of a CPU arena's update,
     logging, tests).  Immutable and hashable: it is part of the one-graph step's cache key."""
 
     KINDS = ('constant', 'step', 'cosine')
@@ -162,8 +162,14 @@ class Optimizer(object):
     """tf.train.MomentumOptimizer(lr, 0.9) | RMSPropOptimizer(lr, 0.9, 0.9) | AdamOptimizer(lr)
     (train.py:114-119) + optional tf.clip_by_global_norm (train.py:127-132), one fused kernel.
 
-    `schedule` (LRSchedule): the rate of update s is schedule.value(s); `lr` stays the base rate.  On a device arena without
-    clipping the rate never passes through the host: begin_step launches rn_lr_schedule_eval, which reads the device step word
+    `grad_clip_norm` C (device arena): the norm is an input of the clipped update, so step() runs one more pass over w and g ahead
+    of it -- rn_grad_norm_partial into `_partial`, rn_norm_reg_finalize into `norm_reg` -- and rn_optimizer_step_clip forms
+    C / max(sqrt(norm_reg[0]), C) from the device scalar itself (_step_clipped).  Rate, bias correction and the average's decay are
+    read from the device exactly as without clipping: the clipped update is recorded into a captured step like the unclipped one.
+    Only a CPU arena (or RN_FUSED_OPT_NORM=0) keeps rn_grad_norm_l2reg + rn_optimizer_step with the rate as a launch argument.
+
+    `schedule` (LRSchedule): the rate of update s is schedule.value(s); `lr` stays the base rate.  On a device arena the rate never
+    passes through the host, with and without clipping: begin_step launches rn_lr_schedule_eval, which reads the device step word
     `step_dev`, leaves [lr(s), the rate the update multiplies by] in `lr_dev` and advances the word; the slices' update kernels read
     lr_dev[1].  No launch argument of such a step changes from one step to the next, Adam's bias correction included.
 
@@ -260,6 +266,10 @@ class Optimizer(object):
             self.step_slice(0, a.count, grad_scale, advance_counter)
             self.finish_step()
             return
+        if a.weights.is_cuda and FUSED_OPT_NORM:
+            self._step_clipped(grad_scale, advance_counter)
+            return
+        # a CPU arena or RN_FUSED_OPT_NORM=0: the norm pass sizes its own workspace and the rate is a launch argument
         L_ = _rn.lib()
         ws = _rn.workspace(L_.rn_optimizer_workspace(a.count), a.weights.device)
         _rn.check(L_.rn_grad_norm_l2reg(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count,
@@ -288,6 +298,33 @@ class Optimizer(object):
                                        ops.DROPOUT_COUNTER_STEP, _rn.stream()), 'rn_optimizer_step')
         import ops_f16
         ops_f16.weights_changed()      # fp16-packed copies of the kernels (inference path) are stale now
+
+    def _step_clipped(self, grad_scale, advance_counter):
+        """The clipped update on a device arena: the norm is an INPUT of the update, so it takes a pass of its own over w and g --
+        into `_partial`, finalised into `norm_reg` -- and the update kernel forms clip / max(sqrt(norm_reg[0]), clip) from the
+        device scalar.  Rate and decay are read from the device like in the unclipped slices (begin_step); nothing here allocates,
+        synchronises or reads a device value, so the sequence is recorded into the one-graph step as it is launched eagerly.  The
+        one launch argument that changes from step to step is Adam's `step` WITHOUT a schedule (Trainer._whole_step_ok)."""
+        a, L_ = self.arena, _rn.lib()
+        self.begin_step()
+        self._pairs = int(L_.rn_optimizer_norm_pairs(a.count))
+        assert 2 * self._pairs <= self._partial.numel()
+        _rn.check(L_.rn_grad_norm_partial(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count, grad_scale,
+                                          self._partial.data_ptr(), _rn.stream()), 'rn_grad_norm_partial')
+        _rn.check(L_.rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),
+                  'rn_norm_reg_finalize')
+        _rn.check(L_.rn_optimizer_step_clip(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
+                                            _rn.f32(self.state2) if self.state2 is not None else None,
+                                            _rn.f32(a.wd_per_block), a.count, self.lr,
+                                            _rn.f32(self.lr_dev) if self.lr_dev is not None else None, grad_scale, self.clip,
+                                            _rn.f32(self.norm_reg), self._update_no,
+                                            advance_counter.data_ptr() if advance_counter is not None else None,
+                                            ops.DROPOUT_COUNTER_STEP,
+                                            _rn.f32(self.ema) if self.ema is not None else None,
+                                            _rn.f32(self.ema_dev) if self.ema is not None else None, _rn.stream()),
+                  'rn_optimizer_step_clip')
+        import ops_f16
+        ops_f16.weights_changed()
 
     # -- the update in slices of the arena (no clipping): Trainer.step updates the heads + FPN slice on a side stream while the
     # backbone's backward pass still runs, the rest after it; every slice's launch leaves its share of (sum g'^2, regulariser)
@@ -546,8 +583,8 @@ class Trainer(object):
             # the kernels are launched on the CURRENT device's current stream with raw pointers
             assert torch.cuda.current_device() == self.device.index, \
                 "call torch.cuda.set_device(%d) before building the Trainer" % self.device.index
-        # (the optimizer kernel is launched per step, outside the captured segments, with the host's step count: Adam's
-        # bias-corrected learning rate is a fresh launch argument every step, also with use_graph=True)
+        # (without an lr_schedule Adam's bias-corrected learning rate is a fresh launch argument every step: its update -- and
+        # RMSProp's -- is then launched per step, outside the captured segments, also with use_graph=True)
         self.loss_mode = loss_mode
         self.arena = ParamArena(net, self.device)
         # lr_schedule (LRSchedule): the rate lives on the device and advances inside the step (Optimizer docstring); None: the
@@ -638,9 +675,9 @@ class Trainer(object):
         # The whole step -- segment A, the collectives, every part of segment B, the update -- is ONE captured graph wherever
         # nothing has to happen on the host between its parts: the ~80 us a step the GPU idles at the graph boundaries and in
         # front of an eagerly launched update (profiles/r05_bench_step_timeline.txt: "idle stretches") disappear.  The update's
-        # host-side scalars are constants of such a graph: momentum SGD without clipping only (no step-dependent scalar), and a
-        # changed learning rate captures again (the rate is part of the cache key).  With an lr_schedule the update has no such
-        # scalar -- rate and Adam's bias correction are read from the device -- so RMSProp and Adam qualify too and the schedule,
+        # host-side scalars are constants of such a graph: momentum SGD only (no step-dependent scalar), and a changed learning
+        # rate or clip value captures again (both are part of the cache key; the clip SCALE is formed on the device from the
+        # norm, with or without a schedule).  With an lr_schedule the update has no such scalar -- rate and Adam's bias correction are read from the device -- so RMSProp and Adam qualify too and the schedule,
         # not a rate, is part of the key.  RN_WHOLE_STEP_GRAPH=0: one graph per part.
         self.schedule = []             # the gradient slices of the last recorded / eager step, in the order their all-reduce was issued
         self._last_lr, self._lr_changes = None, 0
@@ -897,7 +934,8 @@ class Trainer(object):
             all-reduce  [cut_offset, heads_offset)      the FPN's slice             } under segment B
             fork: deferred tower weight gradients  ->  all-reduce [heads_offset, count) behind them, on their stream
             for every part j of the backbone's backward pass, last stage first:  part j  ->  all-reduce of its slice
-            join, wait for the collectives, optimizer update (1 / world folded in; bumps the dropout counter)
+            join, wait for the collectives, optimizer update (1 / world folded in; bumps the dropout counter); with
+            grad_clip_norm the norm pass runs here too, behind the wait: the norm of the REDUCED gradient times 1 / world
 
         Without deferred products the first collective covers [cut_offset, count).  With one rank launch() / wait() do nothing."""
         ar = self.allreduce
@@ -947,7 +985,9 @@ class Trainer(object):
 
     def _capture(self, features):
         """One graph for segment A and one per part of segment B; collectives and the update are eager launches between / after
-        the replays (several ranks whose collectives cannot be captured; RN_WHOLE_STEP_GRAPH=0; Adam / RMSProp / clipping)."""
+        the replays (several ranks whose collectives cannot be captured; RN_WHOLE_STEP_GRAPH=0; Adam / RMSProp at a constant rate,
+        whose update takes a step-dependent launch argument).  Clipping does not bring a step here: the eager update of this path is
+        the very sequence -- Optimizer.step() -- that _capture_whole records."""
         # the captured segments read PRIVATE copies of the features: a caller may hand in other tensors (or reuse these) on
         # later steps -- step() copies them into the static buffers -- and must never find its own tensors overwritten
         self._static = _clone_tree(features)
@@ -978,7 +1018,7 @@ class Trainer(object):
         ar = self.allreduce
         return (self.whole_step_graph and self.use_graph and self.device.type == 'cuda'
                 and (not ar.active or (getattr(ar, 'capturable', False) and not getattr(ar, 'host_staged', False)))
-                and (self.opt.kind == 'momentum' or self.opt.lr_dev is not None) and self.opt.clip <= 0.0 and FUSED_OPT_NORM)
+                and (self.opt.kind == 'momentum' or self.opt.lr_dev is not None) and FUSED_OPT_NORM)
 
     def _capture_whole(self, features):
         """_run_step as ONE graph (see __init__: whole_step_graph): with several ranks the collectives are nodes of it."""
@@ -1013,7 +1053,7 @@ class Trainer(object):
             if self._lr_changes > 3:
                 whole = False
         if whole:
-            key = (key, 'whole', self.opt.schedule if scheduled else self.opt.lr, id(self.allreduce), self.opt.accumulate_steps)
+            key = (key, 'whole', self.opt.schedule if scheduled else self.opt.lr, self.opt.clip, id(self.allreduce), self.opt.accumulate_steps)
         if self.use_graph:
             if self._graphs is None:
                 self._graph_cache.clear()
@@ -1224,7 +1264,9 @@ def build_parser():
     parser.add_argument('--epochs', type=int, default=1)
     parser.add_argument('--scale', type=int, default=256)
     parser.add_argument('--experiment', type=str, default=None, help='directory for checkpoints (model.safetensors)')
-    parser.add_argument('--grad-clip-norm', type=float)
+    parser.add_argument('--grad-clip-norm', type=float, metavar='C',
+                        help='scale the gradient (the L2 regulariser\'s part included) by C / max(its global norm, C); norm and scale '
+                             'are formed on the device, so the update stays inside the captured step; not with --accumulate-steps')
     parser.add_argument('--backbone', type=str, choices=['resnet_50', 'densenet_121', 'densenet_169', 'mobilenet_v2'],
                         default='mobilenet_v2')
     parser.add_argument('--optimizer', type=str, choices=['momentum', 'adam', 'rmsprop'], default='momentum')
@@ -1272,7 +1314,8 @@ def build_parser():
     # gradient accumulation (Optimizer docstring); without --accumulate-steps: an update per step, as before
     parser.add_argument('--accumulate-steps', type=int, default=1, metavar='A',
                         help='apply an update on every A-th step, from the mean of the last A gradients (1 <= A <= 64, default 1: an '
-                             'effective batch A times larger at +4 B per parameter); not with --grad-clip-norm.  --lr-warmup-steps, '
+                             'effective batch A times larger at +4 B per parameter); not with --grad-clip-norm (clipping an accumulated '
+                             'gradient is not implemented; clipping alone stays inside the captured step).  --lr-warmup-steps, '
                              '--lr-decay-steps and --lr-total-steps then count UPDATES, not steps')
     return parser
 
