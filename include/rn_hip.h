@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 414
+#define RN_API_VERSION 415
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -1007,6 +1007,24 @@ int rn_optimizer_step_clip(int kind, float* w, const float* grad, float* state1,
  * `partial`: no workspace, nothing a capture may not contain. */
 int rn_grad_norm_partial(const float* w, const float* grad, const float* wd_per_block, int64_t count, float grad_scale,
                          double* partial, rn_stream_t stream);
+/* A guard against non-finite gradients inside the captured step (the reference trains on whatever its graph computes,
+ * train.py:111-134: a NaN regression target from a ground-truth box of zero extent reaches every weight).  The criterion is the
+ * float rn_norm_reg_finalize leaves: sum g'^2 over the whole arena is not finite iff some g' is NaN or inf or the sum overflows.
+ * One thread: f = isfinite(norm_sq[0]);  gate_dev[0] = 0;  gate_dev[1] = f;  f ? (skipped_dev[1] = 0)
+ * : (skipped_dev[0] += 1, skipped_dev[1] += 1), so skipped_dev = [updates skipped in all, updates skipped in a row].  gate_dev has
+ * the layout of accum_dev: rn_lr_schedule_eval_gated and rn_ema_decay_eval_gated run behind it unchanged, and the step word, the
+ * average's word and Adam's bias correction count APPLIED updates.  No argument changes from step to step.  Checked by the entry:
+ * non-null pointers, norm_sq / gate_dev 4-byte and skipped_dev 8-byte aligned. */
+int rn_finite_gate_eval(const float* norm_sq, int32_t* gate_dev, uint64_t* skipped_dev, rn_stream_t stream);
+/* rn_optimizer_step_clip behind the gate: every wave reads gate_dev[1] once; on 0 the launch bumps advance_counter (fresh dropout
+ * masks next step) and returns without touching w, the slots or ema; otherwise it is rn_optimizer_step_clip's update, bit for
+ * bit.  clip_norm == 0 means no clipping (norm_sq is then not read by the update and may be null).  Checked by the entry before
+ * any launch: non-null, 4-byte aligned gate_dev, clip_norm >= 0, norm_sq with clip_norm > 0, and what rn_optimizer_step_clip
+ * checks of the rest. */
+int rn_optimizer_step_gated(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
+                            int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm, const float* norm_sq,
+                            int64_t step, uint64_t* advance_counter, uint64_t advance_by, float* ema, const float* ema_dev,
+                            const int32_t* gate_dev, rn_stream_t stream);
 /* *counter += inc on the stream (the same counter, for callers that run backward passes without an optimizer step) */
 int rn_counter_add(uint64_t* counter, uint64_t inc, rn_stream_t stream);
 /* p[0..count) = 0 (16-byte aligned): the gradient arena before a backward pass (the reference's graph zero-initialises

@@ -20,7 +20,7 @@ OPT = {"momentum": 0, "rmsprop": 1, "adam": 2}
 OPT_BLOCK = 1024
 LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
-API_VERSION = 414        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 415        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -203,6 +203,7 @@ SYMBOLS = [
     "rn_lr_schedule_eval", "rn_optimizer_step_norm_lrdev", "rn_ema_decay_eval", "rn_optimizer_step_ema",
     "rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated", "rn_optimizer_step_accum",
     "rn_optimizer_step_clip", "rn_grad_norm_partial",
+    "rn_finite_gate_eval", "rn_optimizer_step_gated",
 ]
 
 
@@ -258,6 +259,9 @@ def lib():
         L.rn_optimizer_step_clip.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
                                              C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_grad_norm_partial.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
+        L.rn_finite_gate_eval.argtypes = [C.c_void_p] * 4
+        L.rn_optimizer_step_gated.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_debug_collective_standin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p]
         L.rn_conv2d_stats_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.rn_conv2d_fwd_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -17,7 +17,9 @@ def save(path, net, trainer=None, step=0, extra=None):
     ("model/<name>" stays the raw weights: resuming needs them); readers that know nothing of these keys ignore them.  A trainer
     that accumulates gradients (accumulate_steps A > 1) adds the cycle's running sum PER PARAMETER under "accum/<name>" with metadata
     accum_steps = A and accum_micro = micro-steps taken, so a checkpoint written in the middle of a cycle resumes exactly.  `step`
-    counts micro-steps (the position in the sample stream depends on it), step_count counts updates."""
+    counts micro-steps (the position in the sample stream depends on it), step_count counts updates.  A trainer with the guard
+    against non-finite gradients (skip_nonfinite) is reconciled first (Optimizer.reconcile_skips: this synchronises), so the
+    step_count stored is that of the updates APPLIED, and metadata nonfinite_skipped holds the updates skipped in all."""
     tensors = {"model/" + k: v.detach().cpu().contiguous().clone() for k, v in net.named_parameters()}
     meta = {"step": str(int(step)), "format": "retinanet-amd-v2"}
     if trainer is not None:
@@ -29,6 +31,8 @@ def save(path, net, trainer=None, step=0, extra=None):
                 tensors["optimizer/state2/" + name] = trainer.opt.state2[off:off + size].detach().cpu().clone().view(p.shape)
         # (stored without this replica's offset: every rank adds its own back on load, replicas keep distinct dropout streams)
         tensors["trainer/drop_counter"] = trainer.drop_counter.detach().cpu().clone() - int(getattr(trainer, "drop_rank_offset", 0))
+        if getattr(trainer.opt, "skipped_dev", None) is not None:
+            meta.update(nonfinite_skipped=str(trainer.opt.reconcile_skips()[0]))        # (ahead of step_count below: it corrects it)
         meta.update(optimizer=trainer.opt.kind, step_count=str(trainer.opt.step_count))
         if getattr(trainer.opt, "ema", None) is not None:
             for p, (off, size) in zip(trainer.arena.params, trainer.arena.offsets):
@@ -82,6 +86,9 @@ def load(path, net, trainer=None, use_ema=False):
     that keeps none ignores the keys.  A trainer that accumulates gradients (accumulate_steps A > 1) gets "accum/<name>" and the
     micro-step word back when the file was written with the same A; from any other file (no "accum/" key, or another accum_steps)
     it starts a fresh cycle -- phase 0, the sum cleared -- said once on stderr.  A trainer with A = 1 ignores the keys.
+    A trainer with the guard against non-finite gradients gets its skip count back from nonfinite_skipped (a file without the key:
+    0) -- the device's counter and what the host has accounted for; step_count, the schedule's position and the average's word
+    are those of the updates applied.  A trainer without the guard ignores the key.
     use_ema=True (trainer=None): the net is given the AVERAGES instead of the raw weights, for inference; a file without them
     raises a ValueError."""
     with safe_open(path, framework="pt") as f:
@@ -143,6 +150,8 @@ def load(path, net, trainer=None, use_ema=False):
                                                .to(trainer.drop_counter.device))
                 # (also the device step word of a learning-rate schedule: a resumed run continues the schedule where it stopped)
                 trainer.opt.set_step_count(int(meta.get("step_count", 0)))
+            if trainer is not None and getattr(trainer.opt, "skipped_dev", None) is not None:
+                trainer.opt.set_skipped(int(meta.get("nonfinite_skipped", 0)))
             if want_ema:
                 opt = trainer.opt
                 if has_ema:

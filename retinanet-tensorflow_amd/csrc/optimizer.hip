@@ -52,8 +52,12 @@ __global__ void norm_reg_finalize_kernel(const double* __restrict__ partial, int
 // of three loops: p == 0 and not applying, acc = g * gs (acc is not read); 0 < p and not applying, acc += g * gs; applying, the
 // update from G = (acc + g * gs) * inv_accum in the place of g * gs (acc is not written: the next cycle's first launch overwrites
 // it).  The two accumulating loops touch nothing but acc and leave the block's `partial` pair as the last update wrote it; the
-// dropout counter advances in every launch.  The trailing three arguments are not read by the ACC = false instantiations.
-template <int KIND, bool NORM, bool EMA, bool ACC>
+// dropout counter advances in every launch.  The three accumulation arguments are not read by the ACC = false instantiations.
+// GATE (rn_optimizer_step_gated; never with ACC): `accum_dev` carries gate_dev = [0, finite], what rn_finite_gate_eval left on the
+// device in accum_dev's layout.  Every wave reads its second word once (a uniform load, like lr_dev[1]); on 0 the launch returns
+// behind the dropout counter's bump and touches neither w nor the slots nor ema.  No argument was added for it: the argument
+// block, and with it the code of the GATE = false instantiations, is what it was without the parameter.
+template <int KIND, bool NORM, bool EMA, bool ACC, bool GATE = false>
 __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                      float* __restrict__ s1, float* __restrict__ s2,
                                                      const float* __restrict__ wd, int64_t count, float lr, float gs,
@@ -67,6 +71,10 @@ __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, cons
   float om = 0.f;
   if (EMA) om = ema_dev[1];  // 1 - d(n) of this update, likewise
   if (advance && blockIdx.x == 0 && threadIdx.x == 0) *advance += advance_by;  // the step counter the dropout masks hash (fresh masks next step)
+  static_assert(!(GATE && ACC), "the gate and the accumulation phase share one argument");
+  if (GATE) {
+    if (accum_dev[1] == 0) return;  // gate_dev[1]: a non-finite gradient norm, this step's update does not happen
+  }
   float cs = 1.f;
   if (clip > 0.f) {
     const float gn = sqrtf(norm_sq[0]);
@@ -189,11 +197,13 @@ namespace {
 // lr_dev (optional): the kernel reads its rate from lr_dev[1] -- bias correction included -- and `lr` / `step` are not used
 // ema + ema_dev (optional, both or neither): the EMA instantiations, which also keep the moving average of the weights
 // acc + accum_dev (optional, both or neither; with `partial`): the ACC instantiations, which apply the mean of 1 / inv_accum gradients
+// gate_dev (optional; without `partial` and acc): the GATE instantiations, which do nothing but the counter's bump when gate_dev[1] == 0
 int launch_opt(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block, int64_t count, float lr,
                float grad_scale, float clip_norm, const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
                double* partial, hipStream_t st, const float* lr_dev = nullptr, float* ema = nullptr, const float* ema_dev = nullptr,
-               float* acc = nullptr, float inv_accum = 1.f, const int32_t* accum_dev = nullptr) {
+               float* acc = nullptr, float inv_accum = 1.f, const int32_t* accum_dev = nullptr, const int32_t* gate_dev = nullptr) {
   RN_CHECK_ARG(w && grad && state1 && wd_per_block, "optimizer: null pointer");
+  RN_CHECK_ARG(!gate_dev || (!acc && !accum_dev && !partial), "optimizer: the gate goes with neither accumulation nor the fused norm");
   RN_CHECK_ARG(count > 0 && count % RN_OPT_BLOCK == 0, "optimizer: count %lld not a multiple of %d", (long long)count,
                RN_OPT_BLOCK);
   RN_CHECK_ARG(clip_norm <= 0.f || norm_sq, "optimizer: clipping needs norm_sq");
@@ -209,10 +219,12 @@ int launch_opt(int kind, float* w, const float* grad, float* state1, float* stat
   }
 #define RN_OPT_ARGS                                                                                                            \
   w, grad, state1, state2, wd_per_block, count, lr_eff, grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter,      \
-      (unsigned long long)advance_by, partial, lr_dev, ema, ema_dev, acc, inv_accum, (const int*)accum_dev
+      (unsigned long long)advance_by, partial, lr_dev, ema, ema_dev, acc, inv_accum, (const int*)(gate_dev ? gate_dev : accum_dev)
 #define RN_OPT_LAUNCH(KIND_)                                                                                                    \
   do {                                                                                                                          \
-    if (acc && ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);      \
+    if (gate_dev && ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, true, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
+    else if (gate_dev) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, false, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
+    else if (acc && ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);      \
     else if (acc) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);       \
     else if (ema && partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
     else if (ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);      \
@@ -277,6 +289,21 @@ extern "C" int rn_optimizer_step_clip(int kind, float* w, const float* grad, flo
   // no `partial`: the <KIND, false, EMA, false> instantiations (the norm is this update's INPUT, formed by the pass before it)
   return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter,
                     advance_by, nullptr, (hipStream_t)stream, lr_dev, ema, ema_dev);
+}
+
+extern "C" int rn_optimizer_step_gated(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
+                                       int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm,
+                                       const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by, float* ema,
+                                       const float* ema_dev, const int32_t* gate_dev, rn_stream_t stream) {
+  RN_CHECK_ARG(gate_dev, "optimizer step + gate: null gate_dev");
+  RN_CHECK_ARG(((uintptr_t)gate_dev & 3) == 0, "optimizer step + gate: gate_dev is not 4-byte aligned");
+  RN_CHECK_ARG(clip_norm >= 0.f, "optimizer step + gate: clip_norm %g is below 0 (0: no clipping)", (double)clip_norm);
+  RN_CHECK_ARG(clip_norm == 0.f || norm_sq, "optimizer step + gate: clipping needs norm_sq");
+  RN_CHECK_ARG((ema != nullptr) == (ema_dev != nullptr), "optimizer step + gate: ema and ema_dev go together");
+  RN_CHECK_ARG(!ema || ((uintptr_t)ema & 15) == 0, "optimizer step + gate: ema is not 16-byte aligned");
+  // no `partial`: the <KIND, false, EMA, false, true> instantiations (the norm is the gate's INPUT, formed by the pass before it)
+  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter,
+                    advance_by, nullptr, (hipStream_t)stream, lr_dev, ema, ema_dev, nullptr, 1.f, nullptr, gate_dev);
 }
 
 extern "C" int rn_optimizer_step_accum(int kind, float* w, const float* grad, float* acc, float* state1, float* state2,
@@ -432,6 +459,32 @@ extern "C" int rn_accum_phase_eval(int32_t accumulate_steps, uint64_t* micro_dev
   RN_CHECK_ARG(accumulate_steps >= 1, "accum_phase_eval: accumulate_steps %d < 1", (int)accumulate_steps);
   hipLaunchKernelGGL(accum_phase_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int)accumulate_steps,
                      (unsigned long long*)micro_dev, (int*)accum_dev);
+  RN_LAUNCH_CHECK();
+  return RN_OK;
+}
+
+namespace {
+// gate_dev = [0, sum g'^2 finite]: the layout of accum_dev, so that the gated one-thread kernels above run behind it as they are;
+// skipped_dev = [updates skipped in all, updates skipped in a row] (the second word starts again at an applied update)
+__global__ void finite_gate_eval_kernel(const float* norm_sq, int* gate_dev, unsigned long long* skipped_dev) {
+  const bool finite = isfinite(norm_sq[0]);
+  gate_dev[0] = 0;
+  gate_dev[1] = finite ? 1 : 0;
+  if (finite) {
+    skipped_dev[1] = 0ull;
+  } else {
+    skipped_dev[0] += 1ull;
+    skipped_dev[1] += 1ull;
+  }
+}
+}  // namespace
+
+extern "C" int rn_finite_gate_eval(const float* norm_sq, int32_t* gate_dev, uint64_t* skipped_dev, rn_stream_t stream) {
+  RN_CHECK_ARG(norm_sq && gate_dev && skipped_dev, "finite_gate_eval: null pointer");
+  RN_CHECK_ARG(((uintptr_t)norm_sq & 3) == 0 && ((uintptr_t)gate_dev & 3) == 0 && ((uintptr_t)skipped_dev & 7) == 0,
+               "finite_gate_eval: misaligned pointer (norm_sq 4, gate_dev 4, skipped_dev 8 bytes)");
+  hipLaunchKernelGGL(finite_gate_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, norm_sq, (int*)gate_dev,
+                     (unsigned long long*)skipped_dev);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }

@@ -188,10 +188,28 @@ class Optimizer(object):
     update).  The schedule's and the average's one-thread kernels run behind the same gate, so `step_count`, `step_dev`,
     `ema_updates_dev`, Adam's bias correction and current_lr() all count UPDATES.  On a micro-step that only sums, `norm_reg` (and
     regularization_loss) keep the last update's values.  The dropout counter advances every micro-step.  Again no launch argument
-    changes from one micro-step to the next: one captured graph serves every phase.  With A = 1 none of this is allocated or launched."""
+    changes from one micro-step to the next: one captured graph serves every phase.  With A = 1 none of this is allocated or launched.
+
+    `skip_nonfinite` (default False; device arena, accumulate_steps = 1): a guard.  Every step runs the norm pass over the whole
+    arena ahead of the update (_step_guarded) -- the pass the clipped update runs anyway; without clipping it is one more pass,
+    8 B per parameter -- and the update of a step is SKIPPED iff norm_reg[0], the float rn_norm_reg_finalize leaves, is not finite:
+    a NaN or an inf anywhere in the gradient, or a sum of squares that overflows a float.  rn_finite_gate_eval turns the float into
+    the int32 pair `gate_dev` = [0, finite] and keeps `skipped_dev` = [updates skipped in all, updates skipped in a row]; the
+    schedule's and the average's one-thread kernels and the update (rn_optimizer_step_gated) run behind that gate.  A skipped
+    update leaves the optimizer as if the step had not been taken: w, state1, state2, ema, step_dev, lr_dev, ema_updates_dev and
+    ema_dev keep their bits, and Adam's bias correction counts APPLIED updates.  What does change: the dropout counter advances
+    (fresh masks next step), norm_reg holds the offending step's values (the log shows the non-finite norm) and skipped_dev
+    advances.  Bias correction can count applied updates only on the device, so guarded Adam and RMSProp given no schedule read
+    their rate from the device too (an LRSchedule('constant', learning_rate) built here): a side effect is that they become
+    one-graph steps at a constant rate.  The host never reads a device word inside a step: step_count stays "updates applied" but
+    runs AHEAD by the skips the host has not seen until reconcile_skips() (which synchronises; the training loop calls it where
+    it synchronises anyway, at its log line and at a checkpoint) subtracts them, so between reconciles current_lr() is a log
+    value, not the rate the device applies.  With several ranks the norm is that of the REDUCED gradient: a NaN on any rank
+    reaches every rank's sum, so all ranks take the same decision with no extra collective.  With the guard off none of this is
+    allocated or launched and every path is what it was."""
 
     def __init__(self, arena, kind='momentum', learning_rate=1e-2, grad_clip_norm=None, schedule=None, ema_decay=None,
-                 ema_warmup=True, accumulate_steps=1):
+                 ema_warmup=True, accumulate_steps=1, skip_nonfinite=False):
         assert kind in ['momentum', 'adam', 'rmsprop']
         self.arena, self.kind, self.lr = arena, kind, float(learning_rate)
         self.clip = float(grad_clip_norm) if grad_clip_norm is not None else 0.0
@@ -199,6 +217,16 @@ class Optimizer(object):
         if isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, (int, np.integer)) or accumulate_steps < 1:
             raise ValueError("accumulate_steps %r is not an integer >= 1" % (accumulate_steps,))
         self.accumulate_steps = int(accumulate_steps)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.skip_nonfinite and self.accumulate_steps > 1:
+            raise ValueError("skip_nonfinite with accumulate_steps > 1: a poisoned micro-step would need a decision per cycle, which "
+                             "is not implemented")
+        if self.skip_nonfinite and (dev.type != 'cuda' or not FUSED_OPT_NORM):
+            raise _rn.RnError("skip_nonfinite gates the device's update kernel on the device's norm: it needs a device arena and "
+                              "RN_FUSED_OPT_NORM=1")
+        if self.skip_nonfinite and schedule is None and kind != 'momentum':
+            # the bias correction (and with it the rate the update multiplies by) must count APPLIED updates: from the device
+            schedule = LRSchedule('constant', self.lr)
         if self.accumulate_steps > 1 and self.clip > 0.0:
             raise ValueError("accumulate_steps > 1 with grad_clip_norm: the clipped update takes the norm as an input, and clipping "
                              "an accumulated gradient is not implemented")
@@ -243,6 +271,12 @@ class Optimizer(object):
             self.acc = torch.zeros_like(arena.weights)
             self.micro_dev = torch.zeros(1, dtype=torch.int64, device=dev)          # (the kernel's uint64: same bits)
             self.accum_dev = torch.zeros(2, dtype=torch.int32, device=dev)
+        # the guard's gate and its two counters: HERE as well, for the same reason
+        self.gate_dev = self.skipped_dev = None
+        self._skips_seen = 0            # skipped updates the host's step_count has been corrected for (reconcile_skips)
+        if self.skip_nonfinite:
+            self.gate_dev = torch.zeros(2, dtype=torch.int32, device=dev)
+            self.skipped_dev = torch.zeros(2, dtype=torch.int64, device=dev)        # (the kernel's uint64 pair: same bits)
         self.step_count = 0
 
     def count_step(self):
@@ -260,6 +294,9 @@ class Optimizer(object):
     def step(self, grad_scale=1.0, advance_counter=None):
         """`advance_counter`: the device word the dropout masks hash; bumped by the optimizer kernel itself."""
         a = self.arena
+        if self.skip_nonfinite:
+            self._step_guarded(grad_scale, advance_counter)
+            return
         if self.clip <= 0.0 and a.weights.is_cuda and FUSED_OPT_NORM:
             # no clipping: the norm is not an input of the update -- one pass over the arena forms it beside the update
             self.begin_step()
@@ -325,6 +362,60 @@ class Optimizer(object):
                   'rn_optimizer_step_clip')
         import ops_f16
         ops_f16.weights_changed()
+
+    def _step_guarded(self, grad_scale, advance_counter):
+        """The update behind the guard (skip_nonfinite), clipped or not: norm pass, finalize, rn_finite_gate_eval, then the schedule's
+        and the average's one-thread kernels and the update, all three behind `gate_dev`.  begin_step's UNGATED one-thread kernels
+        do not run on this path: on a skipped step the words they advance must stay.  One stream, nothing allocated, no device
+        value read: the sequence is recorded into the one-graph step as it is launched eagerly, and no launch argument changes
+        from step to step (momentum's constant rate is the only host scalar; Adam and RMSProp read theirs from lr_dev)."""
+        a, L_ = self.arena, _rn.lib()
+        self.count_step()               # (the host counts an update per step; reconcile_skips takes the skipped ones out again)
+        assert self._partial is not None and (self.kind == 'momentum' or self.lr_dev is not None)
+        self._pairs = int(L_.rn_optimizer_norm_pairs(a.count))
+        assert 2 * self._pairs <= self._partial.numel()
+        _rn.check(L_.rn_grad_norm_partial(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count, grad_scale,
+                                          self._partial.data_ptr(), _rn.stream()), 'rn_grad_norm_partial')
+        _rn.check(L_.rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),
+                  'rn_norm_reg_finalize')
+        _rn.check(L_.rn_finite_gate_eval(_rn.f32(self.norm_reg), self.gate_dev.data_ptr(), self.skipped_dev.data_ptr(), _rn.stream()),
+                  'rn_finite_gate_eval')
+        if self.lr_dev is not None:
+            _rn.check(L_.rn_lr_schedule_eval_gated(self._sched_struct, self.step_dev.data_ptr(), _rn.f32(self.lr_dev), _rn.OPT[self.kind],
+                                                   self.gate_dev.data_ptr(), _rn.stream()), 'rn_lr_schedule_eval_gated')
+        if self.ema is not None:
+            _rn.check(L_.rn_ema_decay_eval_gated(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(),
+                                                 _rn.f32(self.ema_dev), self.gate_dev.data_ptr(), _rn.stream()), 'rn_ema_decay_eval_gated')
+        _rn.check(L_.rn_optimizer_step_gated(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
+                                             _rn.f32(self.state2) if self.state2 is not None else None,
+                                             _rn.f32(a.wd_per_block), a.count, self.lr,
+                                             _rn.f32(self.lr_dev) if self.lr_dev is not None else None, grad_scale, self.clip,
+                                             _rn.f32(self.norm_reg), 1,
+                                             advance_counter.data_ptr() if advance_counter is not None else None,
+                                             ops.DROPOUT_COUNTER_STEP,
+                                             _rn.f32(self.ema) if self.ema is not None else None,
+                                             _rn.f32(self.ema_dev) if self.ema is not None else None,
+                                             self.gate_dev.data_ptr(), _rn.stream()), 'rn_optimizer_step_gated')
+        import ops_f16
+        ops_f16.weights_changed()
+
+    def reconcile_skips(self):
+        """(updates skipped in all, updates skipped in a row) from the device -- this SYNCHRONISES -- and step_count brought back to
+        "updates applied": the skips the host had not seen yet are subtracted.  (0, 0) without the guard, and no synchronisation."""
+        if self.skipped_dev is None:
+            return 0, 0
+        total, consecutive = (int(v) for v in self.skipped_dev.tolist())
+        self.step_count -= total - self._skips_seen
+        self._skips_seen = total
+        return total, consecutive
+
+    def set_skipped(self, total):
+        """Updates skipped so far (a restored checkpoint): the device's counter and what the host has accounted for; the run of
+        consecutive skips starts again at 0."""
+        if self.skipped_dev is not None:
+            self.skipped_dev[0] = int(total)
+            self.skipped_dev[1] = 0
+            self._skips_seen = int(total)
 
     # -- the update in slices of the arena (no clipping): Trainer.step updates the heads + FPN slice on a side stream while the
     # backbone's backward pass still runs, the rest after it; every slice's launch leaves its share of (sum g'^2, regulariser)
@@ -574,7 +665,7 @@ class Trainer(object):
                  loss_mode='bce_dice', device='cuda', use_graph=False, process_group=None,
                  direct_param_grads=True, wgrad_side_stream=False, defer_reductions=True, overlap=True,
                  force_collective=False, input_fn=None, check_interval=50, capture_collectives=None, lr_schedule=None,
-                 ema_decay=None, ema_warmup=True, accumulate_steps=1):
+                 ema_decay=None, ema_warmup=True, accumulate_steps=1, skip_nonfinite=False):
         self.net, self.levels = net, levels or build_levels()
         self.device = torch.device(device)
         if self.device.type == 'cuda':
@@ -595,7 +686,12 @@ class Trainer(object):
         # accumulate_steps A: step() is a micro-step, every A-th one applies the mean of the last A gradients (Optimizer docstring).
         # Phase and gate live on the device as well: the step stays ONE graph, captured once and replayed for every phase; A is part
         # of its cache key.  With several ranks every micro-step's gradient is all-reduced (1 / world applied as it is summed)
+        # skip_nonfinite: the update of a step whose global gradient norm is not finite does not happen (Optimizer docstring).  Gate
+        # and counters live on the device: the step stays ONE graph, the guard is part of its cache key, and Adam / RMSProp at a
+        # constant rate read it from the device then, so they qualify for the one-graph step as with an lr_schedule
         ema_kw = {} if ema_decay is None else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}
+        if skip_nonfinite:
+            ema_kw['skip_nonfinite'] = True
         self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule,
                              accumulate_steps=accumulate_steps, **ema_kw)
         self.allreduce = GradientAllReduce(self.arena, process_group, force=force_collective)
@@ -1053,7 +1149,8 @@ class Trainer(object):
             if self._lr_changes > 3:
                 whole = False
         if whole:
-            key = (key, 'whole', self.opt.schedule if scheduled else self.opt.lr, self.opt.clip, id(self.allreduce), self.opt.accumulate_steps)
+            key = (key, 'whole', self.opt.schedule if scheduled else self.opt.lr, self.opt.clip, id(self.allreduce), self.opt.accumulate_steps,
+                   self.opt.skip_nonfinite)
         if self.use_graph:
             if self._graphs is None:
                 self._graph_cache.clear()
@@ -1124,6 +1221,11 @@ class Trainer(object):
         self.last = {'class_loss': class_loss, 'regr_loss': regr_loss,
                      'regularization_loss': self.opt.regularization_loss}
         return self.last
+
+    def skipped_updates(self):
+        """(updates the guard skipped in all, updates skipped in a row up to now) -- (0, 0) without skip_nonfinite.  Synchronises,
+        and brings opt.step_count back to "updates applied" (Optimizer.reconcile_skips)."""
+        return self.opt.reconcile_skips()
 
     @contextlib.contextmanager
     def ema_weights(self):
@@ -1317,6 +1419,15 @@ def build_parser():
                              'effective batch A times larger at +4 B per parameter); not with --grad-clip-norm (clipping an accumulated '
                              'gradient is not implemented; clipping alone stays inside the captured step).  --lr-warmup-steps, '
                              '--lr-decay-steps and --lr-total-steps then count UPDATES, not steps')
+    # guard against non-finite gradients (Optimizer docstring); without --skip-nonfinite: none, as before
+    parser.add_argument('--skip-nonfinite', action='store_true',
+                        help='skip the update of a step whose global gradient norm is not finite (a NaN or inf gradient, or a sum '
+                             'of squares that overflows): weights, optimizer slots, schedule and moving average stay as they '
+                             'are, decided on the device inside the captured step; the log line shows the count; not with '
+                             '--accumulate-steps')
+    parser.add_argument('--nonfinite-limit', type=int, default=None, metavar='N',
+                        help='with --skip-nonfinite: end the run with an error when N updates in a row have been skipped, as seen '
+                             'at a log line or a checkpoint (default: no limit)')
     return parser
 
 
@@ -1327,6 +1438,28 @@ def accumulate_flag_error(args):
     if args.accumulate_steps > 1 and args.grad_clip_norm is not None:
         return '--accumulate-steps with --grad-clip-norm: clipping an accumulated gradient is not implemented'
     return None
+
+
+def guard_flag_error(args):
+    """What is wrong with --skip-nonfinite / --nonfinite-limit as given (checked before any dataset or device is touched), or None."""
+    if args.nonfinite_limit is not None and not args.skip_nonfinite:
+        return '--nonfinite-limit needs --skip-nonfinite'
+    if args.nonfinite_limit is not None and args.nonfinite_limit < 1:
+        return '--nonfinite-limit N: N >= 1 (got %d)' % args.nonfinite_limit
+    if args.skip_nonfinite and args.accumulate_steps > 1:
+        return '--accumulate-steps with --skip-nonfinite: a poisoned micro-step would need a decision per cycle, which is not implemented'
+    return None
+
+
+def check_nonfinite_limit(trainer, limit):
+    """The guard's counters at a point where the training loop synchronises anyway (its log line, a checkpoint; on every rank: all
+    of them see the same counts).  Reconciles the host's update count (Trainer.skipped_updates), returns the updates skipped in all,
+    and raises when `limit` (--nonfinite-limit; None: no limit) or more updates in a row have been skipped."""
+    total, consecutive = trainer.skipped_updates()
+    if limit is not None and consecutive >= limit:
+        raise _rn.RnError("--nonfinite-limit %d: the last %d updates in a row were skipped for a non-finite gradient norm (%d "
+                          "skipped in all): the run ends here" % (limit, consecutive, total))
+    return total
 
 
 def ema_flag_error(args):
@@ -1448,6 +1581,8 @@ def main(argv=None):
         parser.error(ema_flag_error(args))
     if accumulate_flag_error(args):
         parser.error(accumulate_flag_error(args))
+    if guard_flag_error(args):
+        parser.error(guard_flag_error(args))
     K = args.samples_per_step
     if K != 1 and not files:
         parser.error('--samples-per-step groups raw uint8 image files: it needs --dataset pascal ... or coco ...')
@@ -1514,6 +1649,8 @@ def main(argv=None):
     if A > 1 and path is not None and os.path.exists(path):
         # the schedule counts updates: those the file holds, and the run resumes `phase` micro-steps into a cycle
         restored, phase = checkpoint.saved_updates(path, A)
+    elif args.skip_nonfinite and path is not None and os.path.exists(path):
+        restored = checkpoint.saved_updates(path, 1)[0]                           # updates applied: steps less the skipped ones
     try:
         lr_schedule = schedule_from_args(args, steps_per_epoch, restored, phase)
     except ValueError as e:
@@ -1522,7 +1659,10 @@ def main(argv=None):
                       grad_clip_norm=args.grad_clip_norm, loss_mode=args.loss, device=dev, use_graph=not args.no_graph,
                       input_fn=feed, **({'lr_schedule': lr_schedule} if lr_schedule is not None else {}),
                       **({'ema_decay': args.ema_decay, 'ema_warmup': not args.ema_no_warmup} if args.ema_decay is not None else {}),
-                      **({'accumulate_steps': A} if A > 1 else {}))
+                      **({'accumulate_steps': A} if A > 1 else {}), **({'skip_nonfinite': True} if args.skip_nonfinite else {}))
+
+    def skipped():
+        return check_nonfinite_limit(trainer, args.nonfinite_limit)
     step = 0
     if path is not None and os.path.exists(path):
         step = checkpoint.load(path, net, trainer)                                 # every rank reads the same file
@@ -1541,12 +1681,16 @@ def main(argv=None):
             for _ in range(steps_per_epoch):
                 out = trainer.step()                                               # batch = [image, hflip] of a new sample
                 step += 1
+                skips = skipped() if (args.skip_nonfinite and step % 20 == 0) else 0
                 if step % 20 == 0 and rank == 0:
                     print('epoch %d step %d class_loss %.4f regr_loss %.4f reg %.4f lr %.3g' % (
                         epoch, step, out['class_loss'].item(), out['regr_loss'].item(), out['regularization_loss'].item(),
                         trainer.opt.current_lr())                                  # (the rate of the NEXT update: host-side, no sync)
-                          + (' update %d' % trainer.opt.step_count if A > 1 else ''), flush=True)
+                          + (' update %d' % trainer.opt.step_count if A > 1 else '')
+                          + (' skipped %d' % skips if skips > 0 else ''), flush=True)
             trainer.check_device_errors()
+            if args.skip_nonfinite:
+                skipped()
             if args.augment and getattr(loader, 'skipped', 0) != skipped0:
                 raise _rn.RnError("the loader skipped samples while iterating: the augmentation's ordinals no longer equal the "
                                   "stream position a checkpoint stores (samples_drawn)")
@@ -1556,8 +1700,9 @@ def main(argv=None):
     finally:
         feed.close()
     # what the run did, for measuring tools (tools/files_bench.py): wall time of the training loop (captures, checkpoints included)
+    skipped_total = trainer.skipped_updates()[0]                                  # (reconciles: `updates` below counts applied ones)
     LAST_RUN.update(steps=step, seconds=time.perf_counter() - t0, samples=feed.samples_staged, recaptures=trainer.recaptures,
-                    graph_sets=len(trainer._graph_cache), updates=trainer.opt.step_count)
+                    graph_sets=len(trainer._graph_cache), updates=trainer.opt.step_count, skipped=skipped_total)
     if args.eval_images and rank == 0:
         if args.eval_dataset:
             from data_loaders.inferred import Inferred
