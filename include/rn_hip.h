@@ -773,6 +773,14 @@ size_t rn_mb_depthwise_bwd_rows(int n, int h, int w, int c, int stride, int grou
 size_t rn_mb_depthwise_bwd_workspace(int n, int h, int w, int c, int stride);
 int rn_mb_depthwise_bwd(const rn_mb_norm* in, const rn_mb_dy* dy, const float* w, float* dw, const rn_mb_gout* gout, int n, int h,
                         int wd, int stride, void* workspace, size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer);
+/* Which 3x3 tap loops the two depthwise kernels run.  Process-wide switch (default on, RN_MB_DW_TAPS=0 at first use: off).
+ *   on   one base address per pixel and block-uniform tap offsets; the backward data gradient reads no tap that is an exact
+ *        zero (stride 2: 4, 2, 2 or 1 of the nine by the pixel's parity class) and needs no mask
+ *   off  the earlier loops: every tap's index, validity and clamped address per pixel
+ * Same terms in the same order: y, the data gradient, dw and gout->grows / planes are equal either way.  For comparing the
+ * two in one process. */
+int rn_set_mb_dw_taps(int on);
+int rn_get_mb_dw_taps(void);
 
 /* ------------------------------------------------------------------ IoU
  * Replaces utils.iou (utils.py:62-97; known answers utils_test.py:99-118): boxes are corners [y1, x1, y2, x2].

@@ -198,7 +198,7 @@ SYMBOLS = [
     "rn_set_x3_bfrag", "rn_get_x3_bfrag", "rn_x3_bfrag_ok", "rn_x3_bfrag_bytes", "rn_x3_pack_bfrag", "rn_gemm_batched_bfrag", "rn_conv3x3_winograd_gn_u_bytes", "rn_conv3x3_winograd_gn_weights",
     "rn_conv2d_f16_stats_tiles", "rn_group_norm_fwd_f16_tiles",
     "rn_mb_pointwise_bwd_rows", "rn_mb_pointwise_bwd_workspace", "rn_mb_pointwise_bwd",
-    "rn_mb_depthwise_bwd_rows", "rn_mb_depthwise_bwd_workspace", "rn_mb_depthwise_bwd",
+    "rn_mb_depthwise_bwd_rows", "rn_mb_depthwise_bwd_workspace", "rn_mb_depthwise_bwd", "rn_set_mb_dw_taps", "rn_get_mb_dw_taps",
     "rn_debug_collective_standin", "rn_optimizer_norm_pairs", "rn_optimizer_step_norm", "rn_norm_reg_finalize",
     "rn_lr_schedule_eval", "rn_optimizer_step_norm_lrdev", "rn_ema_decay_eval", "rn_optimizer_step_ema",
     "rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated", "rn_optimizer_step_accum",
@@ -316,6 +316,7 @@ def lib():
         L.rn_x3_pack_bfrag.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
         L.rn_gemm_batched_bfrag.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]
         L.rn_set_x3_bfrag.argtypes = [C.c_int]
+        L.rn_set_mb_dw_taps.argtypes = [C.c_int]
         L.rn_conv3x3_winograd_gn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_conv3x3_winograd_gn_bwd_wgrad.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,

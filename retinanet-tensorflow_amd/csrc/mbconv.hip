@@ -13,6 +13,8 @@
 // Pointwise convs run on the fp32 matrix cores (v_mfma_f32_32x32x2_f32, conv_tiles.h); the depthwise kernels stage their
 // input patch through LDS (one transform per element instead of one per tap).  HBM-bound layers: what this file removes is
 // the write + re-read of every normalised tensor and 7 of 13 kernel boundaries per bottleneck.
+#include <type_traits>
+
 #include "mb_common.h"
 
 namespace {
@@ -158,7 +160,8 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void mb_pw_fwd_kernel(const PwFwd
 // depthwise 3x3 forward on the normalised input: block = (sample, TH x TW output tile, channel slab of whole groups)
 // =====================================================================================================================
 
-template <int ACT, bool PF>
+// TAPS: the stencil loop with one base address per output and no division (false: the earlier loop, rn_set_mb_dw_taps(0))
+template <int ACT, bool PF, bool TAPS>
 __global__ __launch_bounds__(T) void mb_dw_fwd_kernel(const DwFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];   // patch [ph * pw][sw]; before / after: merge and reduction scratch
   __shared__ __attribute__((aligned(16))) float tab[2 * 128];    // scale | shift of the slab's channels
@@ -195,6 +198,7 @@ __global__ __launch_bounds__(T) void mb_dw_fwd_kernel(const DwFwdArgs a) {
   };
   load_patch(tile_lo);
   const int lanes = T / SQ, q4 = tid % SQ, pl = tid / SQ;
+  const int step_y = lanes / a.tw, step_x = lanes - step_y * a.tw;      // (oy, ox) of pixel p + lanes from those of pixel p
   float4 wv[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) wv[t] = *reinterpret_cast<const float4*>(a.w + (size_t)t * C + c0 + min(q4, SQ - 1) * 4);
@@ -224,24 +228,54 @@ __global__ __launch_bounds__(T) void mb_dw_fwd_kernel(const DwFwdArgs a) {
     if (PF && tile + 1 < tile_hi) load_patch(tile + 1);
     // stencil from LDS: thread = (channel quad, pixel lane)
     if (pl < lanes) {
-      for (int p = pl; p < a.th * a.tw; p += lanes) {
-        const int oy = p / a.tw, ox = p - oy * a.tw;
-        const int oh_ = oh0 + oy, ow_ = ow0 + ox;
-        if (oh_ < a.oh && ow_ < a.ow) {
-          float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      auto emit = [&](int oh_, int ow_, const float4 acc) {
+        *reinterpret_cast<float4*>(ys + (size_t)(oh_ * a.ow + ow_) * C) = acc;
+        s1[0] += acc.x; s1[1] += acc.y; s1[2] += acc.z; s1[3] += acc.w;
+        s2[0] = fmaf(acc.x, acc.x, s2[0]); s2[1] = fmaf(acc.y, acc.y, s2[1]);
+        s2[2] = fmaf(acc.z, acc.z, s2[2]); s2[3] = fmaf(acc.w, acc.w, s2[3]);
+      };
+      if constexpr (!TAPS) {
+        for (int p = pl; p < a.th * a.tw; p += lanes) {
+          const int oy = p / a.tw, ox = p - oy * a.tw;
+          const int oh_ = oh0 + oy, ow_ = ow0 + ox;
+          if (oh_ < a.oh && ow_ < a.ow) {
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-          for (int kh = 0; kh < 3; ++kh)
+            for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const float4 xv = *reinterpret_cast<const float4*>(&dsm[((size_t)(oy * a.stride + kh) * a.pw + ox * a.stride + kw) * SW + q4 * 4]);
-              const float4 w4 = wv[kh * 3 + kw];
-              acc.x = fmaf(xv.x, w4.x, acc.x); acc.y = fmaf(xv.y, w4.y, acc.y);
-              acc.z = fmaf(xv.z, w4.z, acc.z); acc.w = fmaf(xv.w, w4.w, acc.w);
-            }
-          *reinterpret_cast<float4*>(ys + (size_t)(oh_ * a.ow + ow_) * C) = acc;
-          s1[0] += acc.x; s1[1] += acc.y; s1[2] += acc.z; s1[3] += acc.w;
-          s2[0] = fmaf(acc.x, acc.x, s2[0]); s2[1] = fmaf(acc.y, acc.y, s2[1]);
-          s2[2] = fmaf(acc.z, acc.z, s2[2]); s2[3] = fmaf(acc.w, acc.w, s2[3]);
+              for (int kw = 0; kw < 3; ++kw) {
+                const float4 xv = *reinterpret_cast<const float4*>(&dsm[((size_t)(oy * a.stride + kh) * a.pw + ox * a.stride + kw) * SW + q4 * 4]);
+                const float4 w4 = wv[kh * 3 + kw];
+                acc.x = fmaf(xv.x, w4.x, acc.x); acc.y = fmaf(xv.y, w4.y, acc.y);
+                acc.z = fmaf(xv.z, w4.z, acc.z); acc.w = fmaf(xv.w, w4.w, acc.w);
+              }
+            emit(oh_, ow_, acc);
+          }
+        }
+      } else {
+        // the same pixels in the same order; (oy, ox) advanced by the lane count instead of divided out of p (the forward
+        // planner's tile width need not be a power of two), one base address per output and nine block-uniform offsets
+        const int prow = a.pw * SW;
+        const float* __restrict__ xq = dsm + q4 * 4;
+        int oy = pl / a.tw, ox = pl - oy * a.tw;
+        for (int p = pl; p < a.th * a.tw; p += lanes) {
+          const int oh_ = oh0 + oy, ow_ = ow0 + ox;
+          if (oh_ < a.oh && ow_ < a.ow) {
+            const float* b = xq + (oy * a.pw + ox) * a.stride * SW;
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+              for (int kw = 0; kw < 3; ++kw) {
+                const float4 xv = *reinterpret_cast<const float4*>(b + kh * prow + kw * SW);
+                const float4 w4 = wv[kh * 3 + kw];
+                acc.x = fmaf(xv.x, w4.x, acc.x); acc.y = fmaf(xv.y, w4.y, acc.y);
+                acc.z = fmaf(xv.z, w4.z, acc.z); acc.w = fmaf(xv.w, w4.w, acc.w);
+              }
+            emit(oh_, ow_, acc);
+          }
+          oy += step_y; ox += step_x;
+          if (ox >= a.tw) { ox -= a.tw; ++oy; }
         }
       }
     }
@@ -1096,7 +1130,8 @@ __device__ __forceinline__ int floor_div(int a, int b) { return a >= 0 ? a / b :
 // NPA / NPD: patch loads in flight per thread (input patch / dy patch), sized for the launch's tile and slab by the host (NP is the
 // upper bound any plan may need): the registers they free let PF = the next tile's three raw patches be fetched while this tile's
 // stencils run -- the large maps walk 4 - 8 tiles per block and ran their loop at 2 TB/s with every tile's loads exposed
-template <int ACT, bool MULTI, int S, int NPA = NP, int NPD = NP, bool PF = false>
+// TAPS: the tap loops without per-tap index arithmetic or masks (below); false keeps the earlier loops (rn_set_mb_dw_taps(0))
+template <int ACT, bool MULTI, int S, bool TAPS, int NPA = NP, int NPD = NP, bool PF = false>
 __global__ __launch_bounds__(T, 2) void mb_dw_bwd_kernel(const DwBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];   // a1 patch [(th+2)(tw+2)][sw] | dy patch [oph*opw][sw]
   __shared__ __attribute__((aligned(16))) float tabA[4 * 128];   // scale | shift | mean | rstd of the slab's channels (GN1)
@@ -1214,65 +1249,162 @@ __global__ __launch_bounds__(T, 2) void mb_dw_bwd_kernel(const DwBwdArgs a) {
     if (active) {
       const float4 sc = *reinterpret_cast<const float4*>(&tabA[q4 * 4]), sh = *reinterpret_cast<const float4*>(&tabA[128 + q4 * 4]);
       const float4 mn = *reinterpret_cast<const float4*>(&tabA[256 + q4 * 4]), rs = *reinterpret_cast<const float4*>(&tabA[384 + q4 * 4]);
-      for (int p = pl; p < a.th * a.tw; p += lanes) {
-        const int ty = p >> tw_shift, tx = p - (ty << tw_shift);
-        const int ih = ih0 + ty, iw = iw0 + tx;
-        if (ih < a.h && iw < a.wd) {
-          const float4 yv = *reinterpret_cast<const float4*>(y1 + (size_t)(ih * a.wd + iw) * C);
-          float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      // g1 = d act'(z1) mask of pixel (ih, iw) from its data gradient `acc`, stored, with its share of the per-channel sums
+      auto g1_of = [&](int ih, int iw, const float4 yv, const float4 acc) {
+        const float yy[4] = {yv.x, yv.y, yv.z, yv.w}, dd[4] = {acc.x, acc.y, acc.z, acc.w};
+        const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
+        const float mnv[4] = {mn.x, mn.y, mn.z, mn.w}, rsv[4] = {rs.x, rs.y, rs.z, rs.w};
+        float g[4], mk[4] = {1.f, 1.f, 1.f, 1.f};
+        if (drop) keep4(seed, samp_off + (uint64_t)(ih * a.wd + iw) * C + c0 + q4 * 4, a.in.drop_rate, a.in.keep_scale, mk);
 #pragma unroll
-          for (int kh = 0; kh < 3; ++kh) {
-            const int ohs = ih + a.pad_t - kh;
-            const int oh_ = S == 1 ? ohs : (ohs >> 1);       // (ohs < 0 only with a 0 weight: see m below)
-            const bool rok = ohs >= 0 && oh_ * s == ohs && oh_ < a.oh;
-            const int py = min(max(oh_ - oy0, 0), a.oph - 1);
+        for (int j = 0; j < 4; ++j) {
+          const float z = fmaf(yy[j], scv[j], shv[j]);
+          const float xh = (yy[j] - mnv[j]) * rsv[j];
+          const float t = dd[j] * actgrad_of<ACT>(z, a.in.act) * mk[j];
+          g[j] = t;
+          s1[j] += t; s2[j] = fmaf(t, xh, s2[j]);
+        }
+        *reinterpret_cast<float4*>(go + (size_t)(ih * a.wd + iw) * C) = make_float4(g[0], g[1], g[2], g[3]);
+      };
+      auto tap_w = [&](int t) { return MULTI ? *reinterpret_cast<const float4*>(&wtab[t * 128 + q4 * 4]) : wv[t]; };
+      const float* __restrict__ dq = dyp + q4 * 4;
+      const int drow = a.opw * SW;                         // one row of the dy patch
+      if constexpr (!TAPS) {
+        // the tap loops as they were: every tap's output index, validity and clamped patch address recomputed per pixel
+        for (int p = pl; p < a.th * a.tw; p += lanes) {
+          const int ty = p >> tw_shift, tx = p - (ty << tw_shift);
+          const int ih = ih0 + ty, iw = iw0 + tx;
+          if (ih < a.h && iw < a.wd) {
+            const float4 yv = *reinterpret_cast<const float4*>(y1 + (size_t)(ih * a.wd + iw) * C);
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const int ows = iw + a.pad_l - kw;
-              const int ow_ = S == 1 ? ows : (ows >> 1);
-              const float m = (rok && ows >= 0 && ow_ * s == ows && ow_ < a.ow) ? 1.f : 0.f;
-              const int px = min(max(ow_ - ox0, 0), a.opw - 1);
-              const float4 dv = *reinterpret_cast<const float4*>(&dyp[((size_t)py * a.opw + px) * SW + q4 * 4]);
-              const float4 w4 = MULTI ? *reinterpret_cast<const float4*>(&wtab[(kh * 3 + kw) * 128 + q4 * 4]) : wv[kh * 3 + kw];
-              acc.x = fmaf(dv.x * m, w4.x, acc.x); acc.y = fmaf(dv.y * m, w4.y, acc.y);
-              acc.z = fmaf(dv.z * m, w4.z, acc.z); acc.w = fmaf(dv.w * m, w4.w, acc.w);
+            for (int kh = 0; kh < 3; ++kh) {
+              const int ohs = ih + a.pad_t - kh;
+              const int oh_ = S == 1 ? ohs : (ohs >> 1);       // (ohs < 0 only with a 0 weight: see m below)
+              const bool rok = ohs >= 0 && oh_ * s == ohs && oh_ < a.oh;
+              const int py = min(max(oh_ - oy0, 0), a.oph - 1);
+#pragma unroll
+              for (int kw = 0; kw < 3; ++kw) {
+                const int ows = iw + a.pad_l - kw;
+                const int ow_ = S == 1 ? ows : (ows >> 1);
+                const float m = (rok && ows >= 0 && ow_ * s == ows && ow_ < a.ow) ? 1.f : 0.f;
+                const int px = min(max(ow_ - ox0, 0), a.opw - 1);
+                const float4 dv = *reinterpret_cast<const float4*>(&dyp[((size_t)py * a.opw + px) * SW + q4 * 4]);
+                const float4 w4 = tap_w(kh * 3 + kw);
+                acc.x = fmaf(dv.x * m, w4.x, acc.x); acc.y = fmaf(dv.y * m, w4.y, acc.y);
+                acc.z = fmaf(dv.z * m, w4.z, acc.z); acc.w = fmaf(dv.w * m, w4.w, acc.w);
+              }
             }
+            g1_of(ih, iw, yv, acc);
           }
-          const float yy[4] = {yv.x, yv.y, yv.z, yv.w}, dd[4] = {acc.x, acc.y, acc.z, acc.w};
-          const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
-          const float mnv[4] = {mn.x, mn.y, mn.z, mn.w}, rsv[4] = {rs.x, rs.y, rs.z, rs.w};
-          float g[4], mk[4] = {1.f, 1.f, 1.f, 1.f};
-          if (drop) keep4(seed, samp_off + (uint64_t)(ih * a.wd + iw) * C + c0 + q4 * 4, a.in.drop_rate, a.in.keep_scale, mk);
+        }
+      } else if constexpr (S == 1) {
+        // stride 1 (pad 1 on every side): tap (kh, kw) of tile pixel (ty, tx) is patch element (ty + 2 - kh, tx + 2 - kw) -- the patch
+        // is (th + 2) x (tw + 2) with its origin at output (ih0 - 1, iw0 - 1), so every tap of every tile pixel lies inside it, and
+        // an output outside the image holds 0 there (the patch pass above): no index arithmetic, clamp or mask per tap.  One base
+        // address per pixel (its lowest tap, kh = kw = 2) and nine block-uniform offsets.
+        for (int p = pl; p < a.th * a.tw; p += lanes) {
+          const int ty = p >> tw_shift, tx = p - (ty << tw_shift);
+          const int ih = ih0 + ty, iw = iw0 + tx;
+          if (ih < a.h && iw < a.wd) {
+            const float4 yv = *reinterpret_cast<const float4*>(y1 + (size_t)(ih * a.wd + iw) * C);
+            const float* b = dq + (ty * a.opw + tx) * SW;
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float z = fmaf(yy[j], scv[j], shv[j]);
-            const float xh = (yy[j] - mnv[j]) * rsv[j];
-            const float t = dd[j] * actgrad_of<ACT>(z, a.in.act) * mk[j];
-            g[j] = t;
-            s1[j] += t; s2[j] = fmaf(t, xh, s2[j]);
+            for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+              for (int kw = 0; kw < 3; ++kw) {
+                const float4 dv = *reinterpret_cast<const float4*>(b + (2 - kh) * drow + (2 - kw) * SW);
+                const float4 w4 = tap_w(kh * 3 + kw);
+                acc.x = fmaf(dv.x, w4.x, acc.x); acc.y = fmaf(dv.y, w4.y, acc.y);
+                acc.z = fmaf(dv.z, w4.z, acc.z); acc.w = fmaf(dv.w, w4.w, acc.w);
+              }
+            g1_of(ih, iw, yv, acc);
           }
-          *reinterpret_cast<float4*>(go + (size_t)(ih * a.wd + iw) * C) = make_float4(g[0], g[1], g[2], g[3]);
+        }
+      } else {
+        // stride 2: tap kh reaches an output only where ih + pad_t - kh is even, so a pixel of row class cy = (ih + pad_t) & 1 has
+        // the taps kh = 0, 2 (cy = 0) or kh = 1 (cy = 1), likewise along the width: 4, 2, 2 or 1 of the nine, the others are exact
+        // zeros and are left out (the remaining terms keep their kh, kw order).  The patch row of the class's lowest tap (kh = 2 - cy)
+        // is ((ty + pad_t - cy) >> 1) - pad_t + cy, the other row tap one row further, all inside the (th / 2 + 2)-row patch; outputs
+        // outside the image hold 0 there.  The pixels keep their row-major order and their threads, so every per-thread sum (s1 / s2
+        // behind the rows and planes) adds the same terms in the same order as before: a wave whose pixels are of several classes
+        // runs one masked tap body per class, at most the nine taps of a stride-1 pixel.
+        auto taps_of = [&](auto cy_, auto cx_, const float* b, float4& acc) {
+          constexpr int CY = decltype(cy_)::value, CX = decltype(cx_)::value;
+#pragma unroll
+          for (int kh = CY; kh < 3; kh += 2)
+#pragma unroll
+            for (int kw = CX; kw < 3; kw += 2) {
+              const float4 dv = *reinterpret_cast<const float4*>(b + ((2 - kh) >> 1) * drow + ((2 - kw) >> 1) * SW);
+              const float4 w4 = tap_w(kh * 3 + kw);
+              acc.x = fmaf(dv.x, w4.x, acc.x); acc.y = fmaf(dv.y, w4.y, acc.y);
+              acc.z = fmaf(dv.z, w4.z, acc.z); acc.w = fmaf(dv.w, w4.w, acc.w);
+            }
+        };
+        using I0 = std::integral_constant<int, 0>;
+        using I1 = std::integral_constant<int, 1>;
+        for (int p = pl; p < a.th * a.tw; p += lanes) {
+          const int ty = p >> tw_shift, tx = p - (ty << tw_shift);
+          const int ih = ih0 + ty, iw = iw0 + tx;
+          if (ih < a.h && iw < a.wd) {
+            const float4 yv = *reinterpret_cast<const float4*>(y1 + (size_t)(ih * a.wd + iw) * C);
+            const int cy = (ty + a.pad_t) & 1, cx = (tx + a.pad_l) & 1;
+            const int py = ((ty + a.pad_t - cy) >> 1) - a.pad_t + cy, px = ((tx + a.pad_l - cx) >> 1) - a.pad_l + cx;
+            const float* b = dq + (py * a.opw + px) * SW;
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (cy == 0) {
+              if (cx == 0) taps_of(I0{}, I0{}, b, acc); else taps_of(I0{}, I1{}, b, acc);
+            } else {
+              if (cx == 0) taps_of(I1{}, I0{}, b, acc); else taps_of(I1{}, I1{}, b, acc);
+            }
+            g1_of(ih, iw, yv, acc);
+          }
         }
       }
     }
     // ---- weight-gradient partial sums over the owned outputs (window origin inside the tile)
     if (active) {
-      const int noy = (a.th + s - 1) / s, nox = (a.tw + s - 1) / s;      // tiles are aligned to the stride (host)
-      const int oyb = ih0 / s, oxb = iw0 / s;
-      for (int p = pl; p < noy * nox; p += lanes) {
-        const int ty = p / nox, tx = p - ty * nox;
-        const int oh_ = oyb + ty, ow_ = oxb + tx;
-        if (oh_ < a.oh && ow_ < a.ow) {
-          const float4 dv = *reinterpret_cast<const float4*>(&dyp[((size_t)(oh_ - oy0) * a.opw + (ow_ - ox0)) * SW + q4 * 4]);
+      const int oyb = ih0 / s, oxb = iw0 / s;              // tiles are aligned to the stride (host)
+      if constexpr (!TAPS) {
+        const int noy = (a.th + s - 1) / s, nox = (a.tw + s - 1) / s;
+        for (int p = pl; p < noy * nox; p += lanes) {
+          const int ty = p / nox, tx = p - ty * nox;
+          const int oh_ = oyb + ty, ow_ = oxb + tx;
+          if (oh_ < a.oh && ow_ < a.ow) {
+            const float4 dv = *reinterpret_cast<const float4*>(&dyp[((size_t)(oh_ - oy0) * a.opw + (ow_ - ox0)) * SW + q4 * 4]);
 #pragma unroll
-          for (int kh = 0; kh < 3; ++kh)
+            for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              // input pixel (oh s - pad_t + kh, ..) in a1-patch coordinates (origin ih0 - pad_t)
-              const float4 xv = *reinterpret_cast<const float4*>(&a1p[((size_t)(ty * s + kh) * apw + tx * s + kw) * SW + q4 * 4]);
-              float4& t = wacc[kh * 3 + kw];
-              t.x = fmaf(xv.x, dv.x, t.x); t.y = fmaf(xv.y, dv.y, t.y); t.z = fmaf(xv.z, dv.z, t.z); t.w = fmaf(xv.w, dv.w, t.w);
-            }
+              for (int kw = 0; kw < 3; ++kw) {
+                // input pixel (oh s - pad_t + kh, ..) in a1-patch coordinates (origin ih0 - pad_t)
+                const float4 xv = *reinterpret_cast<const float4*>(&a1p[((size_t)(ty * s + kh) * apw + tx * s + kw) * SW + q4 * 4]);
+                float4& t = wacc[kh * 3 + kw];
+                t.x = fmaf(xv.x, dv.x, t.x); t.y = fmaf(xv.y, dv.y, t.y); t.z = fmaf(xv.z, dv.z, t.z); t.w = fmaf(xv.w, dv.w, t.w);
+              }
+          }
+        }
+      } else {
+        // the same outputs in the same order: th / s x tw / s of them (powers of two: a shift), one base address per output
+        // into either patch and nine block-uniform offsets
+        const int nox_shift = tw_shift - (S - 1), nout = (a.th / s) << nox_shift;
+        const int arow = apw * SW;
+        const float* __restrict__ aq = a1p + q4 * 4;
+        const float* __restrict__ dq = dyp + ((oyb - oy0) * a.opw + (oxb - ox0)) * SW + q4 * 4;
+        for (int p = pl; p < nout; p += lanes) {
+          const int ty = p >> nox_shift, tx = p - (ty << nox_shift);
+          if (oyb + ty < a.oh && oxb + tx < a.ow) {
+            const float4 dv = *reinterpret_cast<const float4*>(dq + (ty * a.opw + tx) * SW);
+            const float* b = aq + (ty * s * apw + tx * s) * SW;        // input pixel (oh s - pad_t, ..) in a1-patch coordinates
+#pragma unroll
+            for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+              for (int kw = 0; kw < 3; ++kw) {
+                const float4 xv = *reinterpret_cast<const float4*>(b + kh * arow + kw * SW);
+                float4& t = wacc[kh * 3 + kw];
+                t.x = fmaf(xv.x, dv.x, t.x); t.y = fmaf(xv.y, dv.y, t.y); t.z = fmaf(xv.z, dv.z, t.z); t.w = fmaf(xv.w, dv.w, t.w);
+              }
+          }
         }
       }
     }
@@ -1325,7 +1457,20 @@ __global__ __launch_bounds__(T, 2) void mb_dw_bwd_kernel(const DwBwdArgs a) {
   }
 }
 
+// ---- which tap loops the depthwise kernels run (rn_set_mb_dw_taps; RN_MB_DW_TAPS=0 at first use: the earlier ones)
+int g_dw_taps = -1;
+int dw_taps_on() {
+  if (g_dw_taps < 0) g_dw_taps = !(getenv("RN_MB_DW_TAPS") && atoi(getenv("RN_MB_DW_TAPS")) == 0);
+  return g_dw_taps;
+}
+
 }  // namespace
+
+extern "C" int rn_set_mb_dw_taps(int on) {
+  g_dw_taps = on ? 1 : 0;
+  return RN_OK;
+}
+extern "C" int rn_get_mb_dw_taps(void) { return dw_taps_on(); }
 
 extern "C" size_t rn_mb_pointwise_rows(int n, int hw, int cin, int cout, int groups, rn_mb_rows* layout) {
   if (n < 1 || hw < 1 || cin < 4 || cout < 4 || groups < 1 || cout % groups) return 0;
@@ -1435,10 +1580,16 @@ extern "C" int rn_mb_depthwise_fwd(const rn_mb_norm* in, const float* w, float* 
   const dim3 grid((unsigned)((long)n * p.nblk * p.nslab));
   hipStream_t st = (hipStream_t)stream;
   static const bool pf = !(getenv("RN_MB_DW_NO_PF") && atoi(getenv("RN_MB_DW_NO_PF")));
-  if (in->act == RN_ACT_ELU && pf && p.tpb > 1) hipLaunchKernelGGL((mb_dw_fwd_kernel<RN_ACT_ELU, true>), grid, dim3(T), lds, st, a);
-  else if (in->act == RN_ACT_ELU) hipLaunchKernelGGL((mb_dw_fwd_kernel<RN_ACT_ELU, false>), grid, dim3(T), lds, st, a);
-  else if (in->act == RN_ACT_RELU6) hipLaunchKernelGGL((mb_dw_fwd_kernel<RN_ACT_RELU6, false>), grid, dim3(T), lds, st, a);
-  else hipLaunchKernelGGL((mb_dw_fwd_kernel<-1, false>), grid, dim3(T), lds, st, a);
+#define RN_DWF(ACT_, PF_)                                                                                              \
+  do {                                                                                                                 \
+    if (dw_taps_on()) hipLaunchKernelGGL((mb_dw_fwd_kernel<ACT_, PF_, true>), grid, dim3(T), lds, st, a);              \
+    else hipLaunchKernelGGL((mb_dw_fwd_kernel<ACT_, PF_, false>), grid, dim3(T), lds, st, a);                          \
+  } while (0)
+  if (in->act == RN_ACT_ELU && pf && p.tpb > 1) RN_DWF(RN_ACT_ELU, true);
+  else if (in->act == RN_ACT_ELU) RN_DWF(RN_ACT_ELU, false);
+  else if (in->act == RN_ACT_RELU6) RN_DWF(RN_ACT_RELU6, false);
+  else RN_DWF(-1, false);
+#undef RN_DWF
   RN_LAUNCH_CHECK();
   return RN_OK;
 }
@@ -1731,28 +1882,33 @@ extern "C" int rn_mb_depthwise_bwd(const rn_mb_norm* in, const rn_mb_dy* dy, con
   RN_UNSUPPORTED(lds > 64 * 1024, "mb depthwise bwd: patches of %zu bytes", lds);
   const dim3 grid((unsigned)((long)nrows * p.nslab));
   hipStream_t st = (hipStream_t)stream;
-  RN_CHECK_ARG((p.tw & (p.tw - 1)) == 0, "mb depthwise bwd: tile width %d is not a power of two", p.tw);
+  // (the kernel's pixel loops shift by the tile's sides, and its stride-2 walk halves them)
+  RN_CHECK_ARG((p.tw & (p.tw - 1)) == 0 && (p.th & (p.th - 1)) == 0 && p.th >= stride && p.tw >= stride,
+               "mb depthwise bwd: tile %d x %d is not a power of two", p.th, p.tw);
+  const bool taps = dw_taps_on();
+#define RN_DWB_S(ACT_, MULTI_, S_, ...)                                                                                \
+  do {                                                                                                                 \
+    if (taps) hipLaunchKernelGGL((mb_dw_bwd_kernel<ACT_, MULTI_, S_, true, ##__VA_ARGS__>), grid, dim3(T), lds, st, a); \
+    else hipLaunchKernelGGL((mb_dw_bwd_kernel<ACT_, MULTI_, S_, false, ##__VA_ARGS__>), grid, dim3(T), lds, st, a);    \
+  } while (0)
 #define RN_DWB(ACT_, MULTI_)                                                                                           \
   do {                                                                                                                 \
-    if (stride == 1) hipLaunchKernelGGL((mb_dw_bwd_kernel<ACT_, MULTI_, 1>), grid, dim3(T), lds, st, a);               \
-    else hipLaunchKernelGGL((mb_dw_bwd_kernel<ACT_, MULTI_, 2>), grid, dim3(T), lds, st, a);                           \
+    if (stride == 1) RN_DWB_S(ACT_, MULTI_, 1);                                                                        \
+    else RN_DWB_S(ACT_, MULTI_, 2);                                                                                    \
   } while (0)
   // (the large maps' launches: loads sized for the plan, next tile prefetched; RN_MB_DWB_PF=0: the plain variant)
   static const bool pf_on = !(getenv("RN_MB_DWB_PF") && atoi(getenv("RN_MB_DWB_PF")) == 0);
   const int npa = rn::ceil_div((p.th + 2) * (p.tw + 2) * (p.sw / 4), T), npd = rn::ceil_div(p.oph * p.opw * (p.sw / 4), T);
-  if (in->act == RN_ACT_ELU && p.tpb > 1 && pf_on && stride == 1 && npa <= 4 && npd <= 4)
-    hipLaunchKernelGGL((mb_dw_bwd_kernel<RN_ACT_ELU, true, 1, 4, 4, true>), grid, dim3(T), lds, st, a);
-  else if (in->act == RN_ACT_ELU && p.tpb > 1 && pf_on && stride == 1 && npa <= 5 && npd <= 5)
-    hipLaunchKernelGGL((mb_dw_bwd_kernel<RN_ACT_ELU, true, 1, 5, 5, true>), grid, dim3(T), lds, st, a);
-  else if (in->act == RN_ACT_ELU && p.tpb > 1 && pf_on && stride == 2 && npa <= 4 && npd <= 2)
-    hipLaunchKernelGGL((mb_dw_bwd_kernel<RN_ACT_ELU, true, 2, 4, 2, true>), grid, dim3(T), lds, st, a);
-  else if (in->act == RN_ACT_ELU && p.tpb > 1 && pf_on && stride == 2 && npa <= 5 && npd <= 2)
-    hipLaunchKernelGGL((mb_dw_bwd_kernel<RN_ACT_ELU, true, 2, 5, 2, true>), grid, dim3(T), lds, st, a);
+  if (in->act == RN_ACT_ELU && p.tpb > 1 && pf_on && stride == 1 && npa <= 4 && npd <= 4) RN_DWB_S(RN_ACT_ELU, true, 1, 4, 4, true);
+  else if (in->act == RN_ACT_ELU && p.tpb > 1 && pf_on && stride == 1 && npa <= 5 && npd <= 5) RN_DWB_S(RN_ACT_ELU, true, 1, 5, 5, true);
+  else if (in->act == RN_ACT_ELU && p.tpb > 1 && pf_on && stride == 2 && npa <= 4 && npd <= 2) RN_DWB_S(RN_ACT_ELU, true, 2, 4, 2, true);
+  else if (in->act == RN_ACT_ELU && p.tpb > 1 && pf_on && stride == 2 && npa <= 5 && npd <= 2) RN_DWB_S(RN_ACT_ELU, true, 2, 5, 2, true);
   else if (in->act == RN_ACT_ELU && p.tpb == 1) RN_DWB(RN_ACT_ELU, false);
   else if (in->act == RN_ACT_ELU) RN_DWB(RN_ACT_ELU, true);
   else if (in->act == RN_ACT_RELU6) RN_DWB(RN_ACT_RELU6, true);
   else RN_DWB(-1, true);
 #undef RN_DWB
+#undef RN_DWB_S
   RN_LAUNCH_CHECK();
   return rn::launch_reduce_rows((const float*)workspace, dw, (int64_t)9 * c, nrows, 0, st);
 }

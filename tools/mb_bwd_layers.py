@@ -1,6 +1,7 @@
 """Per-launch table of the MobileNetV2 chain's BACKWARD pass ("start from evidence") from a rocprofv3
 kernel trace of bench.py (host-side analysis, no GPU needed).
 usage: python tools/mb_bwd_layers.py <bench_kernel_trace.csv> > profiles/r06_mb_bwd_layers.txt
+       python tools/mb_bwd_layers.py <before.csv> <after.csv>     two traces side by side: median and spread per launch
 
 The chain's backward launches of one step come in a fixed order (ops_mb._MbChain.backward): the tail 1x1 conv, then for every
 bottleneck from the last to the first: linear 1x1 (pw), depthwise 3x3 (dw), expand 1x1 (pw) -- 52 launches for 17 bottlenecks.
@@ -102,5 +103,48 @@ def main(path):
         print("#   maps %3d^2: %2d launches %7.1f us (floor %6.1f us, x %.1f, %.1f us per launch)" % (hw, cnt, us, fl, us / fl, us / cnt))
 
 
+def durations(path):
+    """{launch index: sorted durations in us over the traced steps}, {launch index: kernel name} of one trace"""
+    rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r['Start_Timestamp']))
+    marks = [i for i, r in enumerate(rows) if 'assign_kernel' in r['Kernel_Name']]
+    steps = [rows[a:b] for a, b in zip(marks, marks[1:]) if 100 < b - a < 700][-8:]
+    want = expected_launches()
+    per, names = defaultdict(list), {}
+    for st in steps:
+        bw = [r for r in st if re.search(r'mb_(pw|dw)_bwd', r['Kernel_Name'])]
+        if len(bw) != len(want):
+            continue
+        for j, r in enumerate(bw):
+            per[j].append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3)
+            names[j] = short(r['Kernel_Name'])
+    return {j: sorted(d) for j, d in per.items()}, names
+
+
+def compare(path_a, path_b):
+    """Two traces of one box side by side (before | after): per launch the median and the spread (max - min) over the traced
+    steps; `moved` marks a depthwise row whose median changed by more than its own spread (the larger of the two)."""
+    want = expected_launches()
+    (da, _), (db, nb) = durations(path_a), durations(path_b)
+    print("# MobileNetV2 chain, backward pass, cfg 2 (512^2, batch 2), two traces from one box and one call: %s | %s" % (path_a, path_b))
+    print("# median us (spread = max - min) over %d | %d traced steps of rocprofv3 --kernel-trace -- python bench.py --steps 10 --warmup 3" % (len(da[0]), len(db[0])))
+    print("%-3s %-52s %-52s %16s %16s %7s %s" % ("#", "layer", "kernel (after)", "before", "after", "delta", ""))
+    fam = defaultdict(lambda: [0.0, 0.0])
+    for j, (label, kind, _) in enumerate(want):
+        a, b = da[j], db[j]
+        ma, mb = a[len(a) // 2], b[len(b) // 2]
+        spread = max(a[-1] - a[0], b[-1] - b[0])
+        note = ""
+        if kind == "dw" and abs(mb - ma) > spread:
+            note = "slower" if mb > ma else "faster"
+        print("%-3d %-52s %-52s %8.1f (%5.1f) %8.1f (%5.1f) %+7.1f %s" % (j, label, nb[j][:52], ma, a[-1] - a[0], mb, b[-1] - b[0], mb - ma, note))
+        k = re.sub(r'<.*', '', nb[j])
+        fam[k][0] += ma; fam[k][1] += mb
+    for k, (ua, ub) in sorted(fam.items(), key=lambda kv: -kv[1][0]):
+        print("#   %-24s %7.1f us -> %7.1f us (%+.1f)" % (k, ua, ub, ub - ua))
+
+
 if __name__ == "__main__":
-    main(sys.argv[1])
+    if len(sys.argv) > 2:
+        compare(sys.argv[1], sys.argv[2])
+    else:
+        main(sys.argv[1])
