@@ -585,6 +585,57 @@ int rn_loss_fwd(const rn_loss_seg* segs, int nseg, int num_classes, int mode, fl
 int rn_loss_bwd(const rn_loss_seg* segs, int nseg, int num_classes, int mode, const float* stats,
                 const float* g_cls, const float* g_reg, rn_stream_t stream);
 
+/* ------------------------------------------------------------------ running training metrics
+ * Replaces build_metrics (train.py:137-161): the streaming tf.metrics of a training run -- the means of the total, class,
+ * regression and regularisation losses, class_iou = tf.metrics.mean_iou(labels, sigmoid(logits) > 0.5, num_classes=2) over the
+ * trainable anchors, regr_iou = the mean of utils.iou (utils.py:62-97) between the label box and the predicted box, both decoded
+ * (utils.regression_postprocess, utils.py:108-117) at the ground-truth foreground anchors (utils.boxes_decode, utils.py:183-195).
+ * Device-resident: the host reads nothing per step.
+ * Segment = one pyramid level, rows = n*h*w*anchors in [n,h,w,anchors] order; at most RN_MAX_SEG segments. */
+typedef struct rn_metrics_seg {
+  const float* cls_logit;    /* [rows, C]                                       */
+  const float* cls_label;    /* [rows, C] one-hot / zeros                       */
+  const float* reg_pred;     /* [rows, 4] raw (dy, dx, log h, log w)            */
+  const float* reg_label;    /* [rows, 4]                                       */
+  const uint8_t* trainable;  /* [rows] 0/1                                      */
+  const float* anchor_sizes; /* [anchors, 2] (h, w) / image size: rn_decode_boxes' table of this level */
+  int32_t n, h, w, anchors;
+} rn_metrics_seg;
+/* rn_train_metrics_pass: ONE launch over all segments.  For every row with trainable != 0:
+ *   class confusion over the row's C elements: label positive iff label > 0.5, prediction positive iff logit > 0.  `logit > 0`
+ *     stands for the reference's float32 sigmoid(logit) > 0.5: the two differ only for 0 < logit <~ 1.2e-7, where the float32
+ *     sigmoid rounds to exactly 0.5 (the reference then predicts negative, this kernel positive).  Four integer counts.
+ *   box IoU, if the row is foreground (max_c label > 0.5): reg_label and reg_pred decoded with rn_decode_boxes' device function,
+ *     the IoU formed as rn_iou forms it element-wise (float32 op for op; 0 where the intersection is inverted; NaN where the
+ *     reference's is NaN), converted to double and added.
+ * Counts and the IoU sum are reduced wave -> block -> one 64-byte row per block of `workspace` (int64 [tn, fp, fn, tp, iou_rows],
+ * double sum_iou, 2 unused; behind a 64-byte header whose first int64 is the number of rows written).  No atomics, fixed order:
+ * the same bits eagerly and from a graph.  The cls / reg tensors must be 16-byte aligned (16-byte loads where a row's address
+ * allows them, a scalar head and tail otherwise: any C >= 1; C % 4 == 0 up to 128 takes kernels of their own, with every load of
+ * two row groups in flight at once).  workspace: rn_train_metrics_workspace() bytes, 8-byte aligned,
+ * owned by the caller -- it lives from the pass to the fold, so it is NOT the shared scratch arena. */
+size_t rn_train_metrics_workspace(const rn_metrics_seg* segs, int nseg, int num_classes);
+/* the largest value rn_train_metrics_workspace returns (header + 1024 partial rows): a caller whose launches are captured into
+ * graphs allocates this much ONCE, so that every graph of every input shape holds the same pointer for as long as it lives */
+#define RN_TRAIN_METRICS_MAX_WORKSPACE_BYTES 65600
+int rn_train_metrics_pass(const rn_metrics_seg* segs, int nseg, int num_classes, void* workspace, size_t workspace_bytes,
+                          rn_stream_t stream);
+/* rn_train_metrics_fold: one block at the end of the step.  Sums the partial rows the last pass left in `workspace` (never more
+ * than workspace_bytes holds) in a fixed order -- the integer columns exactly, the IoU sums in index order inside 64 contiguous
+ * chunks of rows and then the chunks in order --, reads the device scalars class_loss, regr_loss and reg_loss (the regulariser:
+ * norm_reg[1] of rn_norm_reg_finalize / rn_grad_norm_l2reg) and adds the step into `state` (RN_TRAIN_METRICS_STATE_BYTES, 16-byte
+ * aligned -- checked by this entry and by rn_train_metrics_reset --, device):
+ *   double  [0] sum_total = sum ((class + regr) + reg)  [1] sum_class  [2] sum_regr  [3] sum_reg  [4] sum_iou
+ *   int64   [5] steps  [6] nonfinite_steps  [7] tn  [8] fp  [9] fn  [10] tp  [11] iou_rows
+ * The step is added ONLY IF class_loss, regr_loss, reg_loss and the step's IoU sum are all finite; otherwise nonfinite_steps
+ * advances and nothing else changes (a degenerate box gives NaN as in the reference; one such step must not poison a window's
+ * means).  The gate is the metric's own, independent of rn_finite_gate_eval.  Plain stores. */
+#define RN_TRAIN_METRICS_STATE_BYTES 96
+int rn_train_metrics_fold(const void* workspace, size_t workspace_bytes, const float* class_loss, const float* regr_loss,
+                          const float* reg_loss, void* state, rn_stream_t stream);
+/* state = 0 on the stream (rn_zero over its 96 bytes): a new window */
+int rn_train_metrics_reset(void* state, rn_stream_t stream);
+
 /* ------------------------------------------------------------------ GroupNorm folded into Winograd layers
  * A chain [conv3x3, GroupNorm, activation] x k -> conv3x3 (the class / box subnets, retinanet.py:37-71,85-115; the
  * GroupNorm is normalization.py:20-35) without GroupNorm kernels and without ever writing the normalised tensor:

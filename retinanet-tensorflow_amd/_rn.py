@@ -158,6 +158,17 @@ class LossSeg(C.Structure):
                 ("d_reg_pred", C.c_void_p), ("rows", C.c_int64)]
 
 
+class MetricsSeg(C.Structure):
+    """rn_metrics_seg: one pyramid level of rn_train_metrics_pass"""
+    _fields_ = [("cls_logit", C.c_void_p), ("cls_label", C.c_void_p), ("reg_pred", C.c_void_p), ("reg_label", C.c_void_p),
+                ("trainable", C.c_void_p), ("anchor_sizes", C.c_void_p),
+                ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("anchors", C.c_int32)]
+
+
+TRAIN_METRICS_STATE_BYTES = 96   # RN_TRAIN_METRICS_STATE_BYTES
+TRAIN_METRICS_MAX_WORKSPACE_BYTES = 65600   # RN_TRAIN_METRICS_MAX_WORKSPACE_BYTES
+
+
 class DetLevel(C.Structure):
     _fields_ = [("prob", C.c_void_p), ("boxes", C.c_void_p), ("rows_per_image", C.c_int64),
                 ("regression", C.c_void_p), ("anchor_sizes", C.c_void_p),
@@ -204,6 +215,7 @@ SYMBOLS = [
     "rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated", "rn_optimizer_step_accum",
     "rn_optimizer_step_clip", "rn_grad_norm_partial",
     "rn_finite_gate_eval", "rn_optimizer_step_gated",
+    "rn_train_metrics_workspace", "rn_train_metrics_pass", "rn_train_metrics_fold", "rn_train_metrics_reset",
 ]
 
 
@@ -407,6 +419,14 @@ def lib():
         L.rn_mb_depthwise_bwd_rows.argtypes = [C.c_int] * 6 + [C.c_void_p]
         L.rn_mb_depthwise_bwd_workspace.argtypes = [C.c_int] * 5
         L.rn_mb_depthwise_bwd.argtypes = [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        # (the entries were added without an ABI bump -- no existing entry or struct changed -- so a library of the same version
+        # from before them loads for A/B measurements; metrics.TrainMetrics raises if they are missing)
+        if hasattr(L, "rn_train_metrics_pass"):
+            L.rn_train_metrics_workspace.restype = C.c_size_t
+            L.rn_train_metrics_workspace.argtypes = [C.c_void_p, C.c_int, C.c_int]
+            L.rn_train_metrics_pass.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.rn_train_metrics_fold.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rn_train_metrics_reset.argtypes = [C.c_void_p, C.c_void_p]
         L.rn_same_pad.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rn_same_pad.restype = None
         _lib = L

@@ -6,6 +6,7 @@
 // One thread per anchor (image, cell, anchor).  The [.., C] one-hot rows dominate the bytes
 // (C floats per anchor), so a wave writes the rows of its 64 anchors cooperatively: lane l
 // stores class l (and l+64..) of anchor i for i = 0..63 -- contiguous 4-B stores.
+#include "box_math.h"
 #include "rn_common.h"
 
 namespace {
@@ -25,29 +26,10 @@ struct AssignArgs {
   LevelArgs lv[RN_MAX_LEVELS];
 };
 
-// cell centre i of `size` cells: tf.linspace(cell/2, 1-cell/2, size)[i] in float32
-// (dataset.py:16-25; [TF-sem] value = start + step*i, step = (stop-start)/(size-1))
-__device__ __forceinline__ float cell_center(int i, int size) {
-  const float cell = (float)(1.0 / (double)size);
-  const float start = cell / 2.0f;
-  if (size == 1) return start;
-  const float stop = 1.0f - start;
-  const float step = (stop - start) / (float)(size - 1);
-  const float t = step * (float)i;
-  return start + t;
-}
-
-// utils.iou (utils.py:62-97) of two corner boxes, every float32 operation rounded on its own and in the reference's order
-__device__ __forceinline__ float iou_corners(float a0, float a1, float a2, float a3, float area_a,
-                                             float b0, float b1, float b2, float b3) {
-  const float yt = fmaxf(a0, b0), xl = fmaxf(a1, b1), yb = fminf(a2, b2), xr = fminf(a3, b3);
-  const bool invalid = (yb < yt) || (xr < xl);
-  const float inter = (yb - yt) * (xr - xl);
-  const float area_b = (b2 - b0) * (b3 - b1);
-  const float den = (area_a + area_b) - inter;
-  const float v = inter / den;
-  return invalid ? 0.f : v;
-}
+// the grid's cell centres (dataset.py:16-25) and utils.iou (utils.py:62-97): box_math.h, shared with the decode and the
+// training metrics
+using rn::cell_center;
+using rn::iou_corners;
 
 __global__ __launch_bounds__(T) void iou_kernel(const float4* __restrict__ a, int64_t na, const float4* __restrict__ b,
                                                 int64_t nb, int pairwise, float* __restrict__ out, int32_t* malformed) {

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <string.h>
 
+#include "box_math.h"
 #include "rn_common.h"
 
 namespace {
@@ -531,26 +532,9 @@ __global__ __launch_bounds__(1024) void det_offsets_kernel(const DetArgs a) {
   if (blockIdx.x == gridDim.x - 1 && tid == 0) a.counts[0] = (int64_t)base + total;
 }
 
-// ---- anchor decode (utils.py:108-117)
-__device__ __forceinline__ float cell_center(int i, int size) {
-  const float cell = (float)(1.0 / (double)size);
-  const float start = cell / 2.0f;
-  if (size == 1) return start;
-  const float stop = 1.0f - start;
-  const float step = (stop - start) / (float)(size - 1);
-  const float t = step * (float)i;
-  return start + t;
-}
-
-// one anchor's box from its raw regression (utils.regression_postprocess, utils.py:100-117): the ONLY copy of this
-// arithmetic -- the full-map kernel and the candidate-only path of det_emit_kernel both call it (same bits)
-__device__ __forceinline__ float4 decode_one(const float4 r, float ah, float aw, int y_, int x_, int h, int w) {
-  const float sy = r.x * ah, sx = r.y * aw;
-  const float bh = expf(r.z) * ah, bw = expf(r.w) * aw;
-  const float cy = sy + cell_center(y_, h), cx = sx + cell_center(x_, w);
-  const float hh = bh / 2.0f, hw = bw / 2.0f;
-  return make_float4(cy - hh, cx - hw, cy + hh, cx + hw);
-}
+// ---- anchor decode (utils.py:108-117): one anchor's box from its raw regression is rn::decode_one (box_math.h), the
+// ONLY copy of this arithmetic -- the full-map kernel and the candidate-only path of det_emit_kernel both call it (same bits)
+using rn::decode_one;
 
 constexpr int EMIT_MAXSEG = 8192;
 // ---- 3. emit candidates in anchor order; pad the key array with sentinels

@@ -2,7 +2,8 @@
 of `utils.detect`, and the two IoU metrics of the reference's `build_metrics` (train.py:137-161): `class_iou`
 (tf.metrics.mean_iou, 2 classes, of the thresholded class probabilities) and `regr_iou` (mean IoU between the
 decoded ground-truth and predicted boxes at the foreground anchors).  Host-side numpy on copies of the device
-results: evaluation is not on the training hot path."""
+results: evaluation is not on the training hot path.  `TrainMetrics` keeps the same two definitions, and the means of the
+losses, as running totals on the device DURING training (csrc/train_metrics.hip; train.Trainer(train_metrics=True))."""
 import numpy as np
 
 
@@ -81,6 +82,120 @@ def detections_from_detect(out, num_images):
     """(boxes, scores, class_ids, image_ids, ...) of utils.detect -> per-image tuples for mean_average_precision."""
     boxes, scores, cls, img = (np.asarray(t.detach().cpu().numpy() if hasattr(t, 'detach') else t) for t in out[:4])
     return [(boxes[img == i], scores[img == i], cls[img == i]) for i in range(num_images)]
+
+
+def window_result(sums, counts):
+    """The running metrics from a window's totals (rn_hip.h: the state of rn_train_metrics_fold): `sums` = [sum_total, sum_class,
+    sum_regr, sum_reg, sum_iou], `counts` = [steps, nonfinite_steps, tn, fp, fn, tp, iou_rows].  Totals first, ratios last, as
+    tf.metrics does: class_iou by the rule of `class_iou` below from the confusion counts, regr_iou = sum_iou / iou_rows; nan
+    where the denominator is zero."""
+    sums = [float(v) for v in sums]
+    steps, nonfinite, tn, fp, fn, tp, rows = (int(v) for v in counts)
+    nan = float('nan')
+    ious = []
+    for inter, union in ((tn, tn + fp + fn), (tp, tp + fp + fn)):      # class 0 (negative), class 1 (positive)
+        if union > 0:
+            ious.append(inter / union)
+    mean = lambda s: s / steps if steps > 0 else nan
+    return {'total_loss': mean(sums[0]), 'class_loss': mean(sums[1]), 'regr_loss': mean(sums[2]),
+            'regularization_loss': mean(sums[3]),
+            'class_iou': float(np.mean(ious)) if ious else nan,
+            'regr_iou': sums[4] / rows if rows > 0 else nan,
+            'steps': steps, 'nonfinite_steps': nonfinite}
+
+
+class TrainMetrics(object):
+    """The reference's streaming training metrics (build_metrics, train.py:137-161) kept on the device, inside the step:
+    `update` is one launch over the tensors the loss has just read (csrc/train_metrics.hip: the confusion counts of
+    sigmoid(logit) > 0.5 against the labels over the trainable anchors and the IoU of the label and predicted boxes decoded at
+    the foreground anchors, as one partial row per block), `fold` one block at the end of the step that adds the step -- its
+    losses included -- into the window state unless one of them is not finite.  Both are plain launches on the current stream:
+    nodes of a captured step, with nothing for the host to read.  `result` is the only call that synchronises."""
+
+    def __init__(self, device):
+        import torch
+        import _rn
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise _rn.RnError("the training metrics are accumulated by the device's kernels: they need a device arena")
+        if not hasattr(_rn.lib(), 'rn_train_metrics_pass'):
+            raise _rn.RnError("%s has no rn_train_metrics_pass: rebuild it (make -C retinanet-tensorflow_amd/csrc)" % _rn.LIB_PATH)
+        # doubles [sum_total, sum_class, sum_regr, sum_reg, sum_iou], int64 [steps, nonfinite_steps, tn, fp, fn, tp, iou_rows]
+        self.state = torch.zeros(_rn.TRAIN_METRICS_STATE_BYTES // 8, dtype=torch.int64, device=self.device)
+        # the partial rows: owned (they live from the pass to the fold: not the shared scratch arena) and allocated ONCE at the
+        # largest size any shape needs -- every captured graph holds this pointer in its pass and fold nodes, and a trainer keeps
+        # graphs of several input shapes alive at a time, so the buffer is never replaced
+        self.partial = torch.zeros(_rn.TRAIN_METRICS_MAX_WORKSPACE_BYTES // 8, dtype=torch.int64, device=self.device)
+        self._updated = False
+        self._anchors = {}
+
+    def _anchor_table(self, level, image_size):
+        import utils
+        key = (id(level), tuple(image_size))
+        ent = self._anchors.get(key)
+        if ent is None:                            # (the level is kept alive with its key)
+            ent = self._anchors[key] = (utils._anchor_tensor(
+                level.normalized_anchor_sizes(tuple(image_size), utils.ANCHOR_SIZE_MODE), self.device), level)
+        return ent[0]
+
+    def update(self, labels_trainable, logits_trainable, levels, image_size):
+        """One launch over every level: `labels_trainable` / `logits_trainable` are the `detection_trainable` tuples
+        losses.loss is given (utils.process_labels_and_logits)."""
+        import torch
+        import _rn
+        keys = list(logits_trainable.regression.keys())
+        masks = labels_trainable.trainable_masks
+        segs = (_rn.MetricsSeg * len(keys))()
+        keep = []
+        num_classes = None
+        for i, k in enumerate(keys):
+            z = logits_trainable.classification.unscaled[k].detach().contiguous()
+            l = labels_trainable.classification.prob[k].contiguous()
+            rp = logits_trainable.regression[k].detach().contiguous()
+            rl = labels_trainable.regression[k].contiguous()
+            m = masks[k].contiguous()
+            assert m.dtype in (torch.uint8, torch.bool) and z.dim() == 5 and z.shape == l.shape and rp.shape == rl.shape
+            assert rp.shape == z.shape[:4] + (4,) and m.shape == z.shape[:4]
+            n, h, w, a, c = z.shape
+            assert num_classes in (None, c)
+            num_classes = c
+            anchors = self._anchor_table(levels[k], image_size)
+            assert anchors.shape == (a, 2)
+            segs[i] = _rn.MetricsSeg(_rn.f32(z), _rn.f32(l), _rn.f32(rp), _rn.f32(rl), _rn.ptr(m), _rn.f32(anchors), n, h, w, a)
+            keep.append((z, l, rp, rl, m))
+        L = _rn.lib()
+        need = L.rn_train_metrics_workspace(segs, len(keys), num_classes)
+        if need == 0:
+            raise _rn.RnError("rn_train_metrics_workspace: %s" % L.rn_last_error().decode())
+        assert need <= self.partial.numel() * 8, (need, self.partial.numel() * 8)     # (RN_TRAIN_METRICS_MAX_WORKSPACE_BYTES)
+        self._updated = True
+        _rn.check(L.rn_train_metrics_pass(segs, len(keys), num_classes, self.partial.data_ptr(), self.partial.numel() * 8,
+                                          _rn.stream()), 'rn_train_metrics_pass')
+
+    def fold(self, class_loss, regr_loss, reg_loss):
+        """The end of a step: the pass's partial rows and the three device scalars into the window state (one block)."""
+        import _rn
+        if not self._updated:
+            raise _rn.RnError("TrainMetrics.fold before any update")
+        _rn.check(_rn.lib().rn_train_metrics_fold(self.partial.data_ptr(), self.partial.numel() * 8, _rn.f32(class_loss),
+                                                  _rn.f32(regr_loss), _rn.f32(reg_loss), self.state.data_ptr(), _rn.stream()),
+                  'rn_train_metrics_fold')
+
+    def reset(self):
+        import _rn
+        _rn.check(_rn.lib().rn_train_metrics_reset(self.state.data_ptr(), _rn.stream()), 'rn_train_metrics_reset')
+
+    def raw(self):
+        """(sums [5] float64, counts [7] int64) as numpy; synchronises, one copy."""
+        host = self.state.cpu().numpy()
+        return host[:5].view(np.float64).copy(), host[5:].copy()
+
+    def result(self, reset=True):
+        """The window's metrics (window_result); synchronises and copies the state once.  reset=True starts a new window."""
+        sums, counts = self.raw()
+        if reset:
+            self.reset()
+        return window_result(sums, counts)
 
 
 def class_iou(labels, probs, threshold=0.5):

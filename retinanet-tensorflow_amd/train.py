@@ -665,7 +665,7 @@ class Trainer(object):
                  loss_mode='bce_dice', device='cuda', use_graph=False, process_group=None,
                  direct_param_grads=True, wgrad_side_stream=False, defer_reductions=True, overlap=True,
                  force_collective=False, input_fn=None, check_interval=50, capture_collectives=None, lr_schedule=None,
-                 ema_decay=None, ema_warmup=True, accumulate_steps=1, skip_nonfinite=False):
+                 ema_decay=None, ema_warmup=True, accumulate_steps=1, skip_nonfinite=False, train_metrics=False):
         self.net, self.levels = net, levels or build_levels()
         self.device = torch.device(device)
         if self.device.type == 'cuda':
@@ -694,6 +694,15 @@ class Trainer(object):
             ema_kw['skip_nonfinite'] = True
         self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule,
                              accumulate_steps=accumulate_steps, **ema_kw)
+        # train_metrics: the reference's streaming training metrics (build_metrics, train.py:137-161: loss means, class_iou,
+        # regr_iou) as running totals on the device (metrics.TrainMetrics).  One pass behind the loss over the tensors it has just
+        # read and one block behind the update: two more nodes of the SAME graph(s), or two eager launches; the host reads them only
+        # in train_metrics().  They observe: weights, slots and the dropout counter are bit for bit those of a run without them.
+        # Every micro-step of accumulate_steps counts as a step; the state is rank-local and not stored in checkpoints
+        self.metrics = None
+        if train_metrics:
+            import metrics as _metrics
+            self.metrics = _metrics.TrainMetrics(self.device)        # (raises on a CPU arena)
         self.allreduce = GradientAllReduce(self.arena, process_group, force=force_collective)
         self.use_graph = use_graph
         self.input_fn = input_fn       # optional: features = input_fn(), run INSIDE segment A (e.g. device-side label assignment)
@@ -910,6 +919,9 @@ class Trainer(object):
             inp, logits = utils.process_labels_and_logits(labels=features, logits=logits, levels=self.levels)
             class_loss, regr_loss = losses.loss(labels=inp['detection_trainable'], logits=logits['detection_trainable'],
                                                 mode=self.loss_mode)
+            if self.metrics is not None:       # on this stream, before the backward pass: every tensor it reads is alive and ordered
+                self.metrics.update(inp['detection_trainable'], logits['detection_trainable'], self.levels,
+                                    tuple(features['image'].shape[1:3]))
             # kernels that write a parameter's gradient directly overwrite it; gradients that reach a parameter
             # through autograd (e.g. the concatenated head kernels) are accumulated -> the arena starts at zero
             if not zeroed:
@@ -1063,7 +1075,13 @@ class Trainer(object):
         else:
             grad_scale = ar.wait()
         self.opt.step(grad_scale, self.drop_counter)       # also bumps the dropout counter: fresh masks next step
+        self._fold_metrics(class_loss, regr_loss)
         return class_loss, regr_loss
+
+    def _fold_metrics(self, class_loss, regr_loss):
+        """Behind the update, where norm_reg[1] -- the regulariser the log shows -- is final: the step into the metrics' window."""
+        if self.metrics is not None:
+            self.metrics.fold(class_loss, regr_loss, self.opt.regularization_loss)
 
     def _warm_up(self):
         # warm-up on a side stream (allocator + workspace sizing), then capture; ONE warm-up stream per trainer: every shape
@@ -1206,6 +1224,7 @@ class Trainer(object):
                 else:
                     grad_scale = ar.wait()
                 self.opt.step(grad_scale, self.drop_counter)
+                self._fold_metrics(class_loss, regr_loss)
         else:
             class_loss, regr_loss = self._run_step(features, timed=True)
         if feed is not None:
@@ -1221,6 +1240,13 @@ class Trainer(object):
         self.last = {'class_loss': class_loss, 'regr_loss': regr_loss,
                      'regularization_loss': self.opt.regularization_loss}
         return self.last
+
+    def train_metrics(self, reset=True):
+        """The running metrics over the steps since the last reset (metrics.TrainMetrics.result: total_loss, class_loss, regr_loss,
+        regularization_loss, class_iou, regr_iou, steps, nonfinite_steps).  Synchronises; reset=True starts a new window."""
+        if self.metrics is None:
+            raise ValueError("this trainer keeps no training metrics: build it with train_metrics=True (--train-metrics)")
+        return self.metrics.result(reset=reset)
 
     def skipped_updates(self):
         """(updates the guard skipped in all, updates skipped in a row up to now) -- (0, 0) without skip_nonfinite.  Synchronises,
@@ -1428,7 +1454,19 @@ def build_parser():
     parser.add_argument('--nonfinite-limit', type=int, default=None, metavar='N',
                         help='with --skip-nonfinite: end the run with an error when N updates in a row have been skipped, as seen '
                              'at a log line or a checkpoint (default: no limit)')
+    # running training metrics (metrics.TrainMetrics); without --train-metrics: none, as before
+    parser.add_argument('--train-metrics', action='store_true',
+                        help='keep the means of the losses, class_iou and regr_iou over the steps between two log lines on the '
+                             'device, inside the captured step, and append them to the log line (steps with a non-finite loss or '
+                             'box IoU are left out and counted)')
     return parser
+
+
+def train_metrics_suffix(res):
+    """What --train-metrics appends to the log line: the window's means (Trainer.train_metrics())."""
+    return (' | mean total %.4f class %.4f regr %.4f reg %.4f class_iou %.4f regr_iou %.4f over %d steps' % (
+        res['total_loss'], res['class_loss'], res['regr_loss'], res['regularization_loss'], res['class_iou'], res['regr_iou'],
+        res['steps']) + (' (%d non-finite left out)' % res['nonfinite_steps'] if res['nonfinite_steps'] > 0 else ''))
 
 
 def accumulate_flag_error(args):
@@ -1659,7 +1697,8 @@ def main(argv=None):
                       grad_clip_norm=args.grad_clip_norm, loss_mode=args.loss, device=dev, use_graph=not args.no_graph,
                       input_fn=feed, **({'lr_schedule': lr_schedule} if lr_schedule is not None else {}),
                       **({'ema_decay': args.ema_decay, 'ema_warmup': not args.ema_no_warmup} if args.ema_decay is not None else {}),
-                      **({'accumulate_steps': A} if A > 1 else {}), **({'skip_nonfinite': True} if args.skip_nonfinite else {}))
+                      **({'accumulate_steps': A} if A > 1 else {}), **({'skip_nonfinite': True} if args.skip_nonfinite else {}),
+                      **({'train_metrics': True} if args.train_metrics else {}))
 
     def skipped():
         return check_nonfinite_limit(trainer, args.nonfinite_limit)
@@ -1687,7 +1726,8 @@ def main(argv=None):
                         epoch, step, out['class_loss'].item(), out['regr_loss'].item(), out['regularization_loss'].item(),
                         trainer.opt.current_lr())                                  # (the rate of the NEXT update: host-side, no sync)
                           + (' update %d' % trainer.opt.step_count if A > 1 else '')
-                          + (' skipped %d' % skips if skips > 0 else ''), flush=True)
+                          + (' skipped %d' % skips if skips > 0 else '')
+                          + (train_metrics_suffix(trainer.train_metrics()) if args.train_metrics else ''), flush=True)
             trainer.check_device_errors()
             if args.skip_nonfinite:
                 skipped()
