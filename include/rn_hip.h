@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 415
+#define RN_API_VERSION 416
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -947,22 +947,10 @@ size_t rn_optimizer_workspace(int64_t count);
 /* out[0] = sum(grad^2)*grad_scale^2 (global norm squared), out[1] = sum_b wd_b * 0.5*sum(w^2) */
 int rn_grad_norm_l2reg(const float* w, const float* grad, const float* wd_per_block, int64_t count,
                        float grad_scale, float* out2, void* workspace, size_t workspace_bytes, rn_stream_t stream);
-/* clip_norm <= 0 disables clipping; norm_sq is the device scalar from rn_grad_norm_l2reg.
- * step is 1-based (Adam bias correction). state1/state2: momentum-acc | rms,mom | m,v.
- * advance_counter (optional): a device word incremented by advance_by in the same launch -- the per-step counter the
- * fused dropouts hash (rn_gn_params.drop_seed_dev), so that the next step (or hipGraph replay) draws fresh masks
- * (tf.layers.Dropout draws new noise every session.run, mobilenet_v2.py:62). */
-int rn_optimizer_step(int kind, float* w, const float* grad, float* state1, float* state2,
-                      const float* wd_per_block, int64_t count, float lr, float grad_scale, float clip_norm,
-                      const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by, rn_stream_t stream);
-/* The same update WITHOUT clipping, for a slice [w, w + count) of the arena, that also forms the slice's share of
- * (sum g'^2, L2 regulariser value) in the same pass (one read of w and grad instead of two): rn_optimizer_norm_pairs(count)
- * (double, double) pairs into `partial`; rn_norm_reg_finalize sums the pairs of all slices (fixed order) into out2[2] =
- * what rn_grad_norm_l2reg writes.  A trainer can so update the heads + FPN slice while the backbone's backward pass runs. */
+/* rn_optimizer_norm_pairs(count): the (double, double) pairs of (sum g'^2, L2 regulariser value) that a pass over a slice
+ * [w, w + count) of the arena leaves in `partial` -- the update itself under RN_OPT_F_NORM (below), or rn_grad_norm_partial;
+ * rn_norm_reg_finalize sums the pairs of all slices (fixed order) into out2[2] = what rn_grad_norm_l2reg writes. */
 int64_t rn_optimizer_norm_pairs(int64_t count);
-int rn_optimizer_step_norm(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                           int64_t count, float lr, float grad_scale, int64_t step, uint64_t* advance_counter,
-                           uint64_t advance_by, double* partial, rn_stream_t stream);
 int rn_norm_reg_finalize(const double* partial, int64_t npairs, float* out2, rn_stream_t stream);
 
 /* Learning-rate schedules evaluated ON THE DEVICE (the reference trains at one constant rate, train.py:114-119; its TODO list:
@@ -986,14 +974,9 @@ typedef struct rn_lr_schedule {
   int64_t boundaries[RN_LR_MAX_BOUNDARIES];
 } rn_lr_schedule;
 /* One thread: s = *step_dev;  lr_dev[0] = lr(s);  lr_dev[1] = the rate the update kernel multiplies by -- for RN_OPT_ADAM
- * lr(s) * sqrt(1 - 0.999^t) / (1 - 0.9^t), t = s + 1, formed in double from the rounded lr(s) exactly as rn_optimizer_step forms
- * it from its float argument; lr(s) itself for the other kinds;  *step_dev = s + 1.  No argument changes from step to step. */
+ * lr(s) * sqrt(1 - 0.999^t) / (1 - 0.9^t), t = s + 1, formed in double from the rounded lr(s) exactly as rn_optimizer_update forms
+ * it from its float `lr`; lr(s) itself for the other kinds;  *step_dev = s + 1.  No argument changes from step to step. */
 int rn_lr_schedule_eval(rn_lr_schedule sched, uint64_t* step_dev, float* lr_dev, int optimizer_kind, rn_stream_t stream);
-/* rn_optimizer_step_norm with the rate read from lr_dev[1] (what rn_lr_schedule_eval left there; a launch on another stream must
- * be ordered behind it) instead of a float argument, and hence no `step`: same kernel, same grid, same `partial` layout. */
-int rn_optimizer_step_norm_lrdev(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                                 int64_t count, const float* lr_dev, float grad_scale, uint64_t* advance_counter,
-                                 uint64_t advance_by, double* partial, rn_stream_t stream);
 /* An exponential moving average of the weights, kept by the pass that updates them (tf.train.ExponentialMovingAverage; the
  * reference, train.py:111-134, trains and evaluates the raw weights only).  With n = updates applied before this one and w' the
  * weight after it:
@@ -1005,17 +988,6 @@ int rn_optimizer_step_norm_lrdev(int kind, float* w, const float* grad, float* s
  * changes from step to step, so a replayed hipGraph advances the average by itself.  Checked by the entry: 0 < decay < 1,
  * non-null pointers. */
 int rn_ema_decay_eval(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, rn_stream_t stream);
-/* The optimizer update of train.py:111-134 that also keeps the moving average `ema` (count floats, 16-byte aligned, laid out
- * like w) with 1 - d(n) read from ema_dev[1] (what rn_ema_decay_eval left there; a launch on another stream must be ordered
- * behind it).  The union of the three entries above, every part optional as there: the rate is lr_dev[1] when lr_dev is given,
- * else `lr` (then RN_OPT_ADAM needs step >= 1); clip_norm > 0 needs norm_sq; `partial` (rn_optimizer_norm_pairs(count) pairs,
- * without clipping only) makes the pass form the slice's share of (sum g'^2, regulariser) as rn_optimizer_step_norm does.
- * w, the slots, the pairs and the counter come out exactly as from those entries: the average is one more load, one fused
- * multiply-add and one more store per element (8 B/element). */
-int rn_optimizer_step_ema(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                          int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm, const float* norm_sq,
-                          int64_t step, uint64_t* advance_counter, uint64_t advance_by, double* partial, float* ema,
-                          const float* ema_dev, rn_stream_t stream);
 /* Gradient accumulation inside the captured step (the reference takes one optimizer step per batch, train.py:111-134; a larger
  * effective batch than fits in memory is the usual reason to sum the gradients of A batches first).  A = accumulate_steps; a
  * micro-step is one forward + backward pass, an update is applied on every A-th micro-step, from the MEAN of the last A gradients.
@@ -1032,37 +1004,9 @@ int rn_lr_schedule_eval_gated(rn_lr_schedule sched, uint64_t* step_dev, float* l
                               rn_stream_t stream);
 int rn_ema_decay_eval_gated(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, const int32_t* accum_dev,
                             rn_stream_t stream);
-/* The fused-norm update (rn_optimizer_step_norm / _lrdev / _ema without clipping: `partial` is required; the rate is lr_dev[1] when
- * lr_dev is given, else `lr`, then RN_OPT_ADAM needs step >= 1; ema + ema_dev both or neither) on an accumulated gradient.  Every
- * wave reads accum_dev[0..1] = [p, applying] once and the launch runs ONE of three loops, fp32 per element, gs = grad_scale:
- *   p == 0, not applying   acc  = grad * gs                 acc is not read                              8 B/element
- *   p  > 0, not applying   acc += grad * gs                                                              12 B/element
- *   applying               G = (acc + grad * gs) * inv_accum;  g' = G + wd*w;  the update, the average and the (sum g'^2,
- *                          regulariser) pair exactly as the entries above form them from g'; acc is not written (the next
- *                          cycle's first launch overwrites it)                                           +4 B/element
- * A launch that does not apply leaves w, the slots, ema and its `partial` pairs untouched: rn_norm_reg_finalize then gives the
- * LAST update's (sum g'^2, regulariser) again.  advance_counter is bumped by every launch (fresh dropout masks per micro-step).
- * acc: count floats, 16-byte aligned, laid out like w; zero-filled at the start.  Checked by the entry: what rn_optimizer_step_ema
- * checks, plus non-null acc / accum_dev / partial and 0 < inv_accum <= 1 (the caller passes 1 / A). */
-int rn_optimizer_step_accum(int kind, float* w, const float* grad, float* acc, float* state1, float* state2,
-                            const float* wd_per_block, int64_t count, float lr, const float* lr_dev, float grad_scale,
-                            float inv_accum, const int32_t* accum_dev, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
-                            double* partial, float* ema, const float* ema_dev, rn_stream_t stream);
-/* The CLIPPED update with nothing step-dependent among its launch arguments, so that it can be a node of a captured step like the
- * unclipped entries: clip_scale = clip_norm / max(sqrt(norm_sq[0]), clip_norm) is formed by the kernel from the device scalar, the
- * rate is lr_dev[1] -- bias correction included -- when lr_dev is given (`lr` / `step` are not read then, as in
- * rn_optimizer_step_norm_lrdev), else `lr` exactly as rn_optimizer_step takes it (RN_OPT_ADAM then needs step >= 1, which DOES
- * change from step to step); ema + ema_dev both or neither, as in rn_optimizer_step_ema.  No `partial`: the norm is an input of
- * this pass, so the pass before it forms it (rn_grad_norm_partial + rn_norm_reg_finalize, or rn_grad_norm_l2reg).  Checked by the
- * entry before any launch: clip_norm > 0, non-null norm_sq, ema / ema_dev together and ema 16-byte aligned, count whole blocks,
- * state2 for RN_OPT_RMSPROP / RN_OPT_ADAM, step >= 1 for RN_OPT_ADAM without lr_dev. */
-int rn_optimizer_step_clip(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                           int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm, const float* norm_sq,
-                           int64_t step, uint64_t* advance_counter, uint64_t advance_by, float* ema, const float* ema_dev,
-                           rn_stream_t stream);
 /* The norm pass of rn_grad_norm_l2reg for a SLICE [w, w + count) of the arena (wd_per_block points at the slice's first block):
  * rn_optimizer_norm_pairs(count) (double, double) pairs of (sum g'^2, L2 regulariser value) into `partial`, in the layout
- * rn_optimizer_step_norm writes; rn_norm_reg_finalize over the pairs of all slices gives [sum g'^2, reg].  The caller owns
+ * RN_OPT_F_NORM writes; rn_norm_reg_finalize over the pairs of all slices gives [sum g'^2, reg].  The caller owns
  * `partial`: no workspace, nothing a capture may not contain. */
 int rn_grad_norm_partial(const float* w, const float* grad, const float* wd_per_block, int64_t count, float grad_scale,
                          double* partial, rn_stream_t stream);
@@ -1075,15 +1019,67 @@ int rn_grad_norm_partial(const float* w, const float* grad, const float* wd_per_
  * average's word and Adam's bias correction count APPLIED updates.  No argument changes from step to step.  Checked by the entry:
  * non-null pointers, norm_sq / gate_dev 4-byte and skipped_dev 8-byte aligned. */
 int rn_finite_gate_eval(const float* norm_sq, int32_t* gate_dev, uint64_t* skipped_dev, rn_stream_t stream);
-/* rn_optimizer_step_clip behind the gate: every wave reads gate_dev[1] once; on 0 the launch bumps advance_counter (fresh dropout
- * masks next step) and returns without touching w, the slots or ema; otherwise it is rn_optimizer_step_clip's update, bit for
- * bit.  clip_norm == 0 means no clipping (norm_sq is then not read by the update and may be null).  Checked by the entry before
- * any launch: non-null, 4-byte aligned gate_dev, clip_norm >= 0, norm_sq with clip_norm > 0, and what rn_optimizer_step_clip
- * checks of the rest. */
-int rn_optimizer_step_gated(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                            int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm, const float* norm_sq,
-                            int64_t step, uint64_t* advance_counter, uint64_t advance_by, float* ema, const float* ema_dev,
-                            const int32_t* gate_dev, rn_stream_t stream);
+/* THE UPDATE: one pass over a slice [w, w + count) of the arena (wd_per_block points at the slice's first block), fp32 per element,
+ * float4 accesses, 16 B/element for RN_OPT_MOMENTUM and 20 for the other kinds (w, grad, state1 [, state2] read; all but grad
+ * written).  With g' as above, lr the rate and state1 / state2 = momentum-acc | rms, mom | m, v:
+ *   RN_OPT_MOMENTUM  a = 0.9 a + g';                                       w -= lr a
+ *   RN_OPT_RMSPROP   a = 0.9 a + 0.1 g'^2;  b = 0.9 b + lr g' / sqrt(a + 1e-10);  w -= b
+ *   RN_OPT_ADAM      a = 0.9 a + 0.1 g';    b = 0.999 b + 0.001 g'^2;      w -= lr_t a / (sqrt(b) + 1e-8),
+ *                    lr_t = lr * sqrt(1 - 0.999^step) / (1 - 0.9^step), formed on the host in double; `step` is 1-based
+ * The descriptor lives in host memory and is read before the call returns.  `features` says what the caller means: it selects the
+ * kernel and says which of the fields below the first three lines are set -- the fields of a clear feature stay 0 / null.
+ * Always: kind (enum rn_opt), w, grad, state1, state2 (RN_OPT_RMSPROP / RN_OPT_ADAM), wd_per_block, count, lr, grad_scale, step;
+ *   advance_counter (optional): a device word incremented by advance_by in the same launch -- the per-step counter the fused
+ *   dropouts hash (rn_gn_params.drop_seed_dev), so that the next step (or hipGraph replay) draws fresh masks (tf.layers.Dropout
+ *   draws new noise every session.run, mobilenet_v2.py:62).
+ * RN_OPT_F_NORM   the pass also forms the slice's share of (sum g'^2, L2 regulariser value), both at the weights BEFORE the update
+ *   (one read of w and grad instead of two): rn_optimizer_norm_pairs(count) pairs into `partial`.  No clipping then: the norm is
+ *   not an input.  A trainer can so update the heads + FPN slice while the backbone's backward pass runs.
+ * RN_OPT_F_LRDEV  the rate is lr_dev[1], what rn_lr_schedule_eval left there -- bias correction included -- instead of `lr`; `lr`
+ *   and `step` are not read.  Same kernel, same grid, same `partial` layout.  Without it RN_OPT_ADAM needs step >= 1, an argument
+ *   that DOES change from step to step.
+ * RN_OPT_F_EMA    the pass also keeps the moving average `ema` (count floats, 16-byte aligned, laid out like w) with 1 - d(n) read
+ *   from ema_dev[1], what rn_ema_decay_eval left there.  w, the slots, the pairs and the counter come out exactly as without it:
+ *   the average is one more load, one fused multiply-add and one more store per element (+8 B/element).
+ * RN_OPT_F_CLIP   clip_scale = clip_norm / max(sqrt(norm_sq[0]), clip_norm), formed by the kernel from the device scalar, so
+ *   nothing step-dependent is among the launch arguments and the clipped update can be a node of a captured step like the
+ *   unclipped one.  The norm is an INPUT of this pass, so the pass before it forms it (rn_grad_norm_partial +
+ *   rn_norm_reg_finalize, or rn_grad_norm_l2reg): never with NORM.  Without CLIP clip_norm is 0 and norm_sq null.
+ * RN_OPT_F_ACCUM  (with NORM; never with CLIP or GATE) the update on an accumulated gradient.  Every wave reads accum_dev[0..1] =
+ *   [p, applying], what rn_accum_phase_eval left there, once and the launch runs ONE of three loops, gs = grad_scale:
+ *     p == 0, not applying   acc  = grad * gs                 acc is not read                              8 B/element
+ *     p  > 0, not applying   acc += grad * gs                                                              12 B/element
+ *     applying               G = (acc + grad * gs) * inv_accum;  g' = G + wd*w;  the update, the average and the (sum g'^2,
+ *                            regulariser) pair exactly as formed from g' without ACCUM; acc is not written (the next
+ *                            cycle's first launch overwrites it)                                           +4 B/element
+ *   A launch that does not apply leaves w, the slots, ema and its `partial` pairs untouched: rn_norm_reg_finalize then gives the
+ *   LAST update's (sum g'^2, regulariser) again.  advance_counter is bumped by every launch (fresh dropout masks per micro-step).
+ *   acc: count floats, 16-byte aligned, laid out like w; zero-filled at the start.  inv_accum: the caller passes 1 / A.
+ * RN_OPT_F_GATE   (never with NORM or ACCUM) the update behind the guard's gate: every wave reads gate_dev[1], what
+ *   rn_finite_gate_eval left there, once; on 0 the launch bumps advance_counter (fresh dropout masks next step) and returns without
+ *   touching w, the slots or ema; otherwise it is the ungated update, bit for bit.
+ * A launch on another stream that reads lr_dev / ema_dev / accum_dev must be ordered behind the one-thread kernel that wrote it.
+ * Checked before any launch, each RN_EINVAL with a message: non-null u, w, grad, state1, wd_per_block; count > 0 and whole
+ * blocks; a known kind; state2 for RN_OPT_RMSPROP / RN_OPT_ADAM; no unknown feature bit; NORM with neither CLIP nor GATE; ACCUM
+ * with NORM and with neither CLIP nor GATE; partial non-null iff NORM; lr_dev non-null iff LRDEV; ema and ema_dev both given iff
+ * EMA, ema 16-byte aligned; acc and accum_dev both given iff ACCUM, acc 16-byte aligned, 0 < inv_accum <= 1; gate_dev non-null iff
+ * GATE, 4-byte aligned; clip_norm > 0 and norm_sq with CLIP, clip_norm == 0 and null norm_sq without (NaN refused either way);
+ * step >= 1 for RN_OPT_ADAM without LRDEV.  A pointer that is null by mistake is so refused instead of selecting another kernel. */
+enum rn_opt_feature { RN_OPT_F_NORM = 1, RN_OPT_F_LRDEV = 2, RN_OPT_F_EMA = 4, RN_OPT_F_CLIP = 8,
+                      RN_OPT_F_ACCUM = 16, RN_OPT_F_GATE = 32 };
+typedef struct rn_opt_update {
+  int32_t kind; uint32_t features;
+  float* w; const float* grad; float* state1; float* state2; const float* wd_per_block; int64_t count;
+  float lr; float grad_scale; int64_t step;
+  uint64_t* advance_counter; uint64_t advance_by;
+  double* partial;                                        /* NORM  */
+  const float* lr_dev;                                    /* LRDEV */
+  float* ema; const float* ema_dev;                       /* EMA   */
+  float clip_norm; const float* norm_sq;                  /* CLIP  */
+  float* acc; float inv_accum; const int32_t* accum_dev;  /* ACCUM */
+  const int32_t* gate_dev;                                /* GATE  */
+} rn_opt_update;
+int rn_optimizer_update(const rn_opt_update* u, rn_stream_t stream);
 /* *counter += inc on the stream (the same counter, for callers that run backward passes without an optimizer step) */
 int rn_counter_add(uint64_t* counter, uint64_t inc, rn_stream_t stream);
 /* p[0..count) = 0 (16-byte aligned): the gradient arena before a backward pass (the reference's graph zero-initialises

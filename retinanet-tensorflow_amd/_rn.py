@@ -20,7 +20,8 @@ OPT = {"momentum": 0, "rmsprop": 1, "adam": 2}
 OPT_BLOCK = 1024
 LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
-API_VERSION = 415        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
+API_VERSION = 416        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -32,6 +33,16 @@ class LrSchedule(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_boundaries", C.c_int32), ("base_lr", C.c_double), ("warmup_factor", C.c_double),
                 ("final_factor", C.c_double), ("decay_factor", C.c_double), ("warmup_steps", C.c_int64), ("total_steps", C.c_int64),
                 ("boundaries", C.c_int64 * LR_MAX_BOUNDARIES)]
+
+
+class OptUpdate(C.Structure):
+    """rn_opt_update (passed by pointer, read before rn_optimizer_update returns): the fields of a clear feature stay 0 / None."""
+    _fields_ = [("kind", C.c_int32), ("features", C.c_uint32), ("w", C.c_void_p), ("grad", C.c_void_p), ("state1", C.c_void_p),
+                ("state2", C.c_void_p), ("wd_per_block", C.c_void_p), ("count", C.c_int64), ("lr", C.c_float), ("grad_scale", C.c_float),
+                ("step", C.c_int64), ("advance_counter", C.c_void_p), ("advance_by", C.c_uint64),
+                ("partial", C.c_void_p), ("lr_dev", C.c_void_p), ("ema", C.c_void_p), ("ema_dev", C.c_void_p),       # NORM, LRDEV, EMA
+                ("clip_norm", C.c_float), ("norm_sq", C.c_void_p),                                                   # CLIP
+                ("acc", C.c_void_p), ("inv_accum", C.c_float), ("accum_dev", C.c_void_p), ("gate_dev", C.c_void_p)]  # ACCUM, GATE
 
 
 class ConvSeg(C.Structure):
@@ -203,18 +214,17 @@ SYMBOLS = [
     "rn_loss_workspace", "rn_loss_fwd", "rn_loss_bwd",
     "rn_iou", "rn_anchor_assign", "rn_anchor_assign_levels", "rn_anchor_assign_levels_pair", "rn_decode_boxes", "rn_detect_workspace", "rn_detect",
     "rn_boxes_decode", "rn_nms_classwise_workspace", "rn_nms_classwise",
-    "rn_optimizer_workspace", "rn_grad_norm_l2reg", "rn_optimizer_step", "rn_counter_add", "rn_add_segs",
+    "rn_optimizer_workspace", "rn_grad_norm_l2reg", "rn_optimizer_update", "rn_counter_add", "rn_add_segs",
     "rn_mb_rows_max", "rn_mb_compact_rows_layout", "rn_mb_compact_rows", "rn_mb_pointwise_rows", "rn_mb_pointwise_fwd", "rn_mb_depthwise_rows", "rn_mb_depthwise_fwd", "rn_mb_apply",
     "rn_mb_resident_sync_bytes", "rn_mb_resident_rows", "rn_mb_resident_fwd", "rn_set_product_mode", "rn_get_product_mode",
     "rn_set_x3_bfrag", "rn_get_x3_bfrag", "rn_x3_bfrag_ok", "rn_x3_bfrag_bytes", "rn_x3_pack_bfrag", "rn_gemm_batched_bfrag", "rn_conv3x3_winograd_gn_u_bytes", "rn_conv3x3_winograd_gn_weights",
     "rn_conv2d_f16_stats_tiles", "rn_group_norm_fwd_f16_tiles",
     "rn_mb_pointwise_bwd_rows", "rn_mb_pointwise_bwd_workspace", "rn_mb_pointwise_bwd",
     "rn_mb_depthwise_bwd_rows", "rn_mb_depthwise_bwd_workspace", "rn_mb_depthwise_bwd", "rn_set_mb_dw_taps", "rn_get_mb_dw_taps",
-    "rn_debug_collective_standin", "rn_optimizer_norm_pairs", "rn_optimizer_step_norm", "rn_norm_reg_finalize",
-    "rn_lr_schedule_eval", "rn_optimizer_step_norm_lrdev", "rn_ema_decay_eval", "rn_optimizer_step_ema",
-    "rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated", "rn_optimizer_step_accum",
-    "rn_optimizer_step_clip", "rn_grad_norm_partial",
-    "rn_finite_gate_eval", "rn_optimizer_step_gated",
+    "rn_debug_collective_standin", "rn_optimizer_norm_pairs", "rn_norm_reg_finalize",
+    "rn_lr_schedule_eval", "rn_ema_decay_eval",
+    "rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated",
+    "rn_grad_norm_partial", "rn_finite_gate_eval",
     "rn_train_metrics_workspace", "rn_train_metrics_pass", "rn_train_metrics_fold", "rn_train_metrics_reset",
 ]
 
@@ -254,26 +264,15 @@ def lib():
         L.rn_zero.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.rn_optimizer_norm_pairs.argtypes = [C.c_int64]
         L.rn_optimizer_norm_pairs.restype = C.c_int64
-        L.rn_optimizer_step_norm.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_uint64,
-                                             C.c_void_p, C.c_void_p]
+        L.rn_optimizer_update.argtypes = [C.POINTER(OptUpdate), C.c_void_p]
         L.rn_norm_reg_finalize.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.rn_lr_schedule_eval.argtypes = [LrSchedule, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.rn_optimizer_step_norm_lrdev.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_uint64,
-                                                   C.c_void_p, C.c_void_p]
         L.rn_ema_decay_eval.argtypes = [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rn_optimizer_step_ema.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
-                                            C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_accum_phase_eval.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_lr_schedule_eval_gated.argtypes = [LrSchedule, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.rn_ema_decay_eval_gated.argtypes = [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rn_optimizer_step_accum.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_int64, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
-                                              C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rn_optimizer_step_clip.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
-                                             C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_grad_norm_partial.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
         L.rn_finite_gate_eval.argtypes = [C.c_void_p] * 4
-        L.rn_optimizer_step_gated.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
-                                              C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_debug_collective_standin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p]
         L.rn_conv2d_stats_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.rn_conv2d_fwd_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
@@ -393,9 +392,6 @@ def lib():
                                                                                         C.c_void_p]
         L.rn_grad_norm_l2reg.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
                                                              C.c_size_t, C.c_void_p]
-        L.rn_optimizer_step.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float,
-                                                                       C.c_float, C.c_void_p, C.c_int64,
-                                                                       C.c_void_p, C.c_uint64, C.c_void_p]
         L.rn_counter_add.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
         L.rn_add_segs.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         for name in ("rn_mb_pointwise_rows", "rn_mb_depthwise_rows", "rn_mb_pointwise_bwd_rows", "rn_mb_pointwise_bwd_workspace",

@@ -47,13 +47,13 @@ __global__ void norm_reg_finalize_kernel(const double* __restrict__ partial, int
 // EMA: the pass also keeps the exponential moving average of the weights (tf.train.ExponentialMovingAverage): with w' the
 // weight this launch stores and om = ema_dev[1] = 1 - d(n), what rn_ema_decay_eval left on the device, e <- e - (e - w') * om.
 // The two EMA arguments are not read by the EMA = false instantiations.
-// ACC (rn_optimizer_step_accum): the pass sums the gradients of A launches in `acc` and applies their mean on the A-th.  Every wave
+// ACC (RN_OPT_F_ACCUM): the pass sums the gradients of A launches in `acc` and applies their mean on the A-th.  Every wave
 // reads accum_dev = [p, applying], what rn_accum_phase_eval left on the device, once (a uniform load, like lr_dev[1]) and runs ONE
 // of three loops: p == 0 and not applying, acc = g * gs (acc is not read); 0 < p and not applying, acc += g * gs; applying, the
 // update from G = (acc + g * gs) * inv_accum in the place of g * gs (acc is not written: the next cycle's first launch overwrites
 // it).  The two accumulating loops touch nothing but acc and leave the block's `partial` pair as the last update wrote it; the
 // dropout counter advances in every launch.  The three accumulation arguments are not read by the ACC = false instantiations.
-// GATE (rn_optimizer_step_gated; never with ACC): `accum_dev` carries gate_dev = [0, finite], what rn_finite_gate_eval left on the
+// GATE (RN_OPT_F_GATE; never with ACC): `accum_dev` carries gate_dev = [0, finite], what rn_finite_gate_eval left on the
 // device in accum_dev's layout.  Every wave reads its second word once (a uniform load, like lr_dev[1]); on 0 the launch returns
 // behind the dropout counter's bump and touches neither w nor the slots nor ema.  No argument was added for it: the argument
 // block, and with it the code of the GATE = false instantiations, is what it was without the parameter.
@@ -193,42 +193,58 @@ extern "C" int rn_grad_norm_partial(const float* w, const float* grad, const flo
   return RN_OK;
 }
 
-namespace {
-// lr_dev (optional): the kernel reads its rate from lr_dev[1] -- bias correction included -- and `lr` / `step` are not used
-// ema + ema_dev (optional, both or neither): the EMA instantiations, which also keep the moving average of the weights
-// acc + accum_dev (optional, both or neither; with `partial`): the ACC instantiations, which apply the mean of 1 / inv_accum gradients
-// gate_dev (optional; without `partial` and acc): the GATE instantiations, which do nothing but the counter's bump when gate_dev[1] == 0
-int launch_opt(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block, int64_t count, float lr,
-               float grad_scale, float clip_norm, const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
-               double* partial, hipStream_t st, const float* lr_dev = nullptr, float* ema = nullptr, const float* ema_dev = nullptr,
-               float* acc = nullptr, float inv_accum = 1.f, const int32_t* accum_dev = nullptr, const int32_t* gate_dev = nullptr) {
-  RN_CHECK_ARG(w && grad && state1 && wd_per_block, "optimizer: null pointer");
-  RN_CHECK_ARG(!gate_dev || (!acc && !accum_dev && !partial), "optimizer: the gate goes with neither accumulation nor the fused norm");
-  RN_CHECK_ARG(count > 0 && count % RN_OPT_BLOCK == 0, "optimizer: count %lld not a multiple of %d", (long long)count,
-               RN_OPT_BLOCK);
-  RN_CHECK_ARG(clip_norm <= 0.f || norm_sq, "optimizer: clipping needs norm_sq");
-  RN_CHECK_ARG(kind == RN_OPT_MOMENTUM || state2, "optimizer: state2 required for rmsprop/adam");
-  const unsigned nb = grid_for(count / 4);
-  float lr_eff = lr;
-  if (kind == RN_OPT_ADAM && !lr_dev) {
-    RN_CHECK_ARG(step >= 1, "optimizer: adam step must be >= 1");
-    lr_eff = (float)((double)lr * sqrt(1.0 - pow(0.999, (double)step)) / (1.0 - pow(0.9, (double)step)));
-  } else if (kind != RN_OPT_MOMENTUM && kind != RN_OPT_RMSPROP && kind != RN_OPT_ADAM) {
-    rn::set_error("optimizer: unknown kind %d", kind);
-    return RN_EINVAL;
+extern "C" int64_t rn_optimizer_norm_pairs(int64_t count) { return count > 0 ? (int64_t)grid_for(count / 4) : 0; }
+
+// The one update entry: `features` says which instantiation runs and which fields must be set -- a pointer that is null (or set)
+// by mistake is refused, it does not select another kernel.  Every check stands ahead of the launch (include/rn_hip.h lists them).
+extern "C" int rn_optimizer_update(const rn_opt_update* u, rn_stream_t stream) {
+  RN_CHECK_ARG(u, "optimizer: null descriptor");
+  const uint32_t f = u->features;
+  const bool norm = f & RN_OPT_F_NORM, lrdev = f & RN_OPT_F_LRDEV, ema = f & RN_OPT_F_EMA, clip = f & RN_OPT_F_CLIP,
+             accum = f & RN_OPT_F_ACCUM, gate = f & RN_OPT_F_GATE;
+  const int kind = u->kind;
+  const int64_t count = u->count;
+  RN_CHECK_ARG(u->w && u->grad && u->state1 && u->wd_per_block, "optimizer: null pointer");
+  RN_CHECK_ARG(count > 0 && count % RN_OPT_BLOCK == 0, "optimizer: count %lld not a multiple of %d", (long long)count, RN_OPT_BLOCK);
+  RN_CHECK_ARG(kind == RN_OPT_MOMENTUM || kind == RN_OPT_RMSPROP || kind == RN_OPT_ADAM, "optimizer: unknown kind %d", kind);
+  RN_CHECK_ARG(kind == RN_OPT_MOMENTUM || u->state2, "optimizer: state2 required for rmsprop/adam");
+  RN_CHECK_ARG(!(f & ~(uint32_t)(RN_OPT_F_NORM | RN_OPT_F_LRDEV | RN_OPT_F_EMA | RN_OPT_F_CLIP | RN_OPT_F_ACCUM | RN_OPT_F_GATE)),
+               "optimizer: unknown feature bit in 0x%x", (unsigned)f);
+  RN_CHECK_ARG(!norm || (!clip && !gate), "optimizer: NORM (the fused norm) goes with neither CLIP nor GATE: the norm is their input");
+  RN_CHECK_ARG(!accum || (norm && !clip && !gate), "optimizer: ACCUM needs NORM and goes with neither CLIP nor GATE");
+  RN_CHECK_ARG((u->partial != nullptr) == norm, "optimizer: partial is set with NORM and only with it");
+  RN_CHECK_ARG((u->lr_dev != nullptr) == lrdev, "optimizer: lr_dev (the device rate) is set with LRDEV and only with it");
+  RN_CHECK_ARG((u->ema != nullptr) == ema && (u->ema_dev != nullptr) == ema, "optimizer: ema and ema_dev go together, with EMA and only with it");
+  RN_CHECK_ARG(((uintptr_t)u->ema & 15) == 0, "optimizer: ema is not 16-byte aligned");
+  RN_CHECK_ARG((u->acc != nullptr) == accum && (u->accum_dev != nullptr) == accum,
+               "optimizer: acc and accum_dev go together, with ACCUM and only with it");
+  RN_CHECK_ARG(((uintptr_t)u->acc & 15) == 0, "optimizer: acc is not 16-byte aligned");
+  RN_CHECK_ARG(!accum || (u->inv_accum > 0.f && u->inv_accum <= 1.f), "optimizer: inv_accum %g outside (0, 1]", (double)u->inv_accum);
+  RN_CHECK_ARG((u->gate_dev != nullptr) == gate, "optimizer: gate_dev is set with GATE and only with it");
+  RN_CHECK_ARG(((uintptr_t)u->gate_dev & 3) == 0, "optimizer: gate_dev is not 4-byte aligned");
+  RN_CHECK_ARG(clip ? u->clip_norm > 0.f : u->clip_norm == 0.f, "optimizer: clip_norm %g (above 0 with CLIP, 0 without)", (double)u->clip_norm);
+  RN_CHECK_ARG((u->norm_sq != nullptr) == clip, "optimizer: norm_sq is set with CLIP and only with it");
+  float lr_eff = u->lr;  // LRDEV: the kernel reads its rate from lr_dev[1] -- bias correction included -- and `lr` / `step` are not used
+  if (kind == RN_OPT_ADAM && !lrdev) {
+    RN_CHECK_ARG(u->step >= 1, "optimizer: adam step must be >= 1");
+    lr_eff = (float)((double)u->lr * sqrt(1.0 - pow(0.999, (double)u->step)) / (1.0 - pow(0.9, (double)u->step)));
   }
-#define RN_OPT_ARGS                                                                                                            \
-  w, grad, state1, state2, wd_per_block, count, lr_eff, grad_scale, clip_norm, norm_sq, (unsigned long long*)advance_counter,      \
-      (unsigned long long)advance_by, partial, lr_dev, ema, ema_dev, acc, inv_accum, (const int*)(gate_dev ? gate_dev : accum_dev)
+  const unsigned nb = grid_for(count / 4);
+  hipStream_t st = (hipStream_t)stream;
+  // the gate travels in accum_dev's slot (never both); inv_accum is 1 without ACCUM
+#define RN_OPT_ARGS                                                                                                              \
+  u->w, u->grad, u->state1, u->state2, u->wd_per_block, count, lr_eff, u->grad_scale, u->clip_norm, u->norm_sq,                   \
+      (unsigned long long*)u->advance_counter, (unsigned long long)u->advance_by, u->partial, u->lr_dev, u->ema, u->ema_dev, u->acc, \
+      accum ? u->inv_accum : 1.f, (const int*)(gate ? u->gate_dev : u->accum_dev)
 #define RN_OPT_LAUNCH(KIND_)                                                                                                    \
   do {                                                                                                                          \
-    if (gate_dev && ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, true, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
-    else if (gate_dev) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, false, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
-    else if (acc && ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);      \
-    else if (acc) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);       \
-    else if (ema && partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
+    if (gate && ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, true, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
+    else if (gate) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, false, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
+    else if (accum && ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);   \
+    else if (accum) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false, true>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);     \
+    else if (ema && norm) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS); \
     else if (ema) hipLaunchKernelGGL((opt_step_kernel<KIND_, false, true, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);      \
-    else if (partial) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);  \
+    else if (norm) hipLaunchKernelGGL((opt_step_kernel<KIND_, true, false, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);     \
     else hipLaunchKernelGGL((opt_step_kernel<KIND_, false, false, false>), dim3(nb), dim3(T), 0, st, RN_OPT_ARGS);              \
   } while (0)
   if (kind == RN_OPT_MOMENTUM) RN_OPT_LAUNCH(RN_OPT_MOMENTUM);
@@ -238,86 +254,6 @@ int launch_opt(int kind, float* w, const float* grad, float* state1, float* stat
 #undef RN_OPT_ARGS
   RN_LAUNCH_CHECK();
   return RN_OK;
-}
-}  // namespace
-
-extern "C" int rn_optimizer_step(int kind, float* w, const float* grad, float* state1, float* state2,
-                                 const float* wd_per_block, int64_t count, float lr, float grad_scale, float clip_norm,
-                                 const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by, rn_stream_t stream) {
-  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter, advance_by,
-                    nullptr, (hipStream_t)stream);
-}
-
-extern "C" int64_t rn_optimizer_norm_pairs(int64_t count) { return count > 0 ? (int64_t)grid_for(count / 4) : 0; }
-
-extern "C" int rn_optimizer_step_norm(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                                      int64_t count, float lr, float grad_scale, int64_t step, uint64_t* advance_counter,
-                                      uint64_t advance_by, double* partial, rn_stream_t stream) {
-  RN_CHECK_ARG(partial, "optimizer step + norm: null partial buffer");
-  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, 0.f, nullptr, step, advance_counter, advance_by,
-                    partial, (hipStream_t)stream);
-}
-
-extern "C" int rn_optimizer_step_norm_lrdev(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                                            int64_t count, const float* lr_dev, float grad_scale, uint64_t* advance_counter,
-                                            uint64_t advance_by, double* partial, rn_stream_t stream) {
-  RN_CHECK_ARG(partial, "optimizer step + norm: null partial buffer");
-  RN_CHECK_ARG(lr_dev, "optimizer step + norm: null device rate");
-  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, 0.f, grad_scale, 0.f, nullptr, 0, advance_counter, advance_by,
-                    partial, (hipStream_t)stream, lr_dev);
-}
-
-extern "C" int rn_optimizer_step_ema(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                                     int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm,
-                                     const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by,
-                                     double* partial, float* ema, const float* ema_dev, rn_stream_t stream) {
-  RN_CHECK_ARG(ema && ema_dev, "optimizer step + ema: null ema / ema_dev");
-  RN_CHECK_ARG(((uintptr_t)ema & 15) == 0, "optimizer step + ema: ema is not 16-byte aligned");
-  RN_CHECK_ARG(!(partial && clip_norm > 0.f), "optimizer step + ema: the fused norm (partial) is formed without clipping");
-  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter,
-                    advance_by, partial, (hipStream_t)stream, lr_dev, ema, ema_dev);
-}
-
-extern "C" int rn_optimizer_step_clip(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                                      int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm,
-                                      const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by, float* ema,
-                                      const float* ema_dev, rn_stream_t stream) {
-  RN_CHECK_ARG(clip_norm > 0.f, "optimizer step + clip: clip_norm %g is not above 0", (double)clip_norm);
-  RN_CHECK_ARG(norm_sq, "optimizer step + clip: null norm_sq");
-  RN_CHECK_ARG((ema != nullptr) == (ema_dev != nullptr), "optimizer step + clip: ema and ema_dev go together");
-  RN_CHECK_ARG(!ema || ((uintptr_t)ema & 15) == 0, "optimizer step + clip: ema is not 16-byte aligned");
-  // no `partial`: the <KIND, false, EMA, false> instantiations (the norm is this update's INPUT, formed by the pass before it)
-  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter,
-                    advance_by, nullptr, (hipStream_t)stream, lr_dev, ema, ema_dev);
-}
-
-extern "C" int rn_optimizer_step_gated(int kind, float* w, const float* grad, float* state1, float* state2, const float* wd_per_block,
-                                       int64_t count, float lr, const float* lr_dev, float grad_scale, float clip_norm,
-                                       const float* norm_sq, int64_t step, uint64_t* advance_counter, uint64_t advance_by, float* ema,
-                                       const float* ema_dev, const int32_t* gate_dev, rn_stream_t stream) {
-  RN_CHECK_ARG(gate_dev, "optimizer step + gate: null gate_dev");
-  RN_CHECK_ARG(((uintptr_t)gate_dev & 3) == 0, "optimizer step + gate: gate_dev is not 4-byte aligned");
-  RN_CHECK_ARG(clip_norm >= 0.f, "optimizer step + gate: clip_norm %g is below 0 (0: no clipping)", (double)clip_norm);
-  RN_CHECK_ARG(clip_norm == 0.f || norm_sq, "optimizer step + gate: clipping needs norm_sq");
-  RN_CHECK_ARG((ema != nullptr) == (ema_dev != nullptr), "optimizer step + gate: ema and ema_dev go together");
-  RN_CHECK_ARG(!ema || ((uintptr_t)ema & 15) == 0, "optimizer step + gate: ema is not 16-byte aligned");
-  // no `partial`: the <KIND, false, EMA, false, true> instantiations (the norm is the gate's INPUT, formed by the pass before it)
-  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, clip_norm, norm_sq, step, advance_counter,
-                    advance_by, nullptr, (hipStream_t)stream, lr_dev, ema, ema_dev, nullptr, 1.f, nullptr, gate_dev);
-}
-
-extern "C" int rn_optimizer_step_accum(int kind, float* w, const float* grad, float* acc, float* state1, float* state2,
-                                       const float* wd_per_block, int64_t count, float lr, const float* lr_dev, float grad_scale,
-                                       float inv_accum, const int32_t* accum_dev, int64_t step, uint64_t* advance_counter,
-                                       uint64_t advance_by, double* partial, float* ema, const float* ema_dev, rn_stream_t stream) {
-  RN_CHECK_ARG(acc && accum_dev, "optimizer step + accumulation: null acc / accum_dev");
-  RN_CHECK_ARG(((uintptr_t)acc & 15) == 0, "optimizer step + accumulation: acc is not 16-byte aligned");
-  RN_CHECK_ARG(partial, "optimizer step + accumulation: null partial buffer (the fused-norm path only)");
-  RN_CHECK_ARG((ema != nullptr) == (ema_dev != nullptr), "optimizer step + accumulation: ema and ema_dev go together");
-  RN_CHECK_ARG(!ema || ((uintptr_t)ema & 15) == 0, "optimizer step + accumulation: ema is not 16-byte aligned");
-  RN_CHECK_ARG(inv_accum > 0.f && inv_accum <= 1.f, "optimizer step + accumulation: inv_accum %g outside (0, 1]", (double)inv_accum);
-  return launch_opt(kind, w, grad, state1, state2, wd_per_block, count, lr, grad_scale, 0.f, nullptr, step, advance_counter, advance_by,
-                    partial, (hipStream_t)stream, lr_dev, ema, ema_dev, acc, inv_accum, accum_dev);
 }
 
 namespace {

@@ -1160,7 +1160,7 @@ DROPOUT_COUNTER_STEP = 0x9E3779B9
 
 def advance_dropout_counter(counter):
     """Next step's dropout masks: bump the device-side word every fused dropout hashes with.  train.Trainer.step does not
-    need this (its optimizer kernel bumps the counter, rn_optimizer_step); it is for backward passes without an update."""
+    need this (its optimizer kernel bumps the counter, rn_optimizer_update); it is for backward passes without an update."""
     _rn.check(_rn.lib().rn_counter_add(counter.data_ptr(), DROPOUT_COUNTER_STEP, _rn.stream()), "rn_counter_add")
 
 

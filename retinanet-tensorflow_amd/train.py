@@ -163,10 +163,11 @@ class Optimizer(object):
     (train.py:114-119) + optional tf.clip_by_global_norm (train.py:127-132), one fused kernel.
 
     `grad_clip_norm` C (device arena): the norm is an input of the clipped update, so step() runs one more pass over w and g ahead
-    of it -- rn_grad_norm_partial into `_partial`, rn_norm_reg_finalize into `norm_reg` -- and rn_optimizer_step_clip forms
+    of it -- rn_grad_norm_partial into `_partial`, rn_norm_reg_finalize into `norm_reg` -- and the update (RN_OPT_F_CLIP) forms
     C / max(sqrt(norm_reg[0]), C) from the device scalar itself (_step_clipped).  Rate, bias correction and the average's decay are
     read from the device exactly as without clipping: the clipped update is recorded into a captured step like the unclipped one.
-    Only a CPU arena (or RN_FUSED_OPT_NORM=0) keeps rn_grad_norm_l2reg + rn_optimizer_step with the rate as a launch argument.
+    Only a CPU arena (or RN_FUSED_OPT_NORM=0) keeps rn_grad_norm_l2reg + rn_optimizer_update without RN_OPT_F_LRDEV: the rate
+    is a launch argument.  Which features an optimizer's updates carry follows from its constructor's arguments: `_features`.
 
     `schedule` (LRSchedule): the rate of update s is schedule.value(s); `lr` stays the base rate.  On a device arena the rate never
     passes through the host, with and without clipping: begin_step launches rn_lr_schedule_eval, which reads the device step word
@@ -183,7 +184,7 @@ class Optimizer(object):
     is a MICRO-step; an update is applied on every A-th one, from the mean of the last A gradients (each already times grad_scale).
     The backward kernels overwrite a parameter's gradient slot, so the sum lives in an arena of its own, `acc` (+4 B per parameter),
     kept by the update kernel: begin_step launches rn_accum_phase_eval, which leaves [p, p == A - 1] in `accum_dev` from the device
-    word `micro_dev` (p = micro-steps so far mod A) and advances the word; rn_optimizer_step_accum reads the pair and either only
+    word `micro_dev` (p = micro-steps so far mod A) and advances the word; the update (RN_OPT_F_ACCUM) reads the pair and either only
     sums (acc = g or acc += g: 8 / 12 B per element, nothing else touched) or applies (acc + g) / A (+4 B per element over the plain
     update).  The schedule's and the average's one-thread kernels run behind the same gate, so `step_count`, `step_dev`,
     `ema_updates_dev`, Adam's bias correction and current_lr() all count UPDATES.  On a micro-step that only sums, `norm_reg` (and
@@ -195,7 +196,7 @@ class Optimizer(object):
     8 B per parameter -- and the update of a step is SKIPPED iff norm_reg[0], the float rn_norm_reg_finalize leaves, is not finite:
     a NaN or an inf anywhere in the gradient, or a sum of squares that overflows a float.  rn_finite_gate_eval turns the float into
     the int32 pair `gate_dev` = [0, finite] and keeps `skipped_dev` = [updates skipped in all, updates skipped in a row]; the
-    schedule's and the average's one-thread kernels and the update (rn_optimizer_step_gated) run behind that gate.  A skipped
+    schedule's and the average's one-thread kernels and the update (RN_OPT_F_GATE) run behind that gate.  A skipped
     update leaves the optimizer as if the step had not been taken: w, state1, state2, ema, step_dev, lr_dev, ema_updates_dev and
     ema_dev keep their bits, and Adam's bias correction counts APPLIED updates.  What does change: the dropout counter advances
     (fresh masks next step), norm_reg holds the offending step's values (the log shows the non-finite norm) and skipped_dev
@@ -277,7 +278,38 @@ class Optimizer(object):
         if self.skip_nonfinite:
             self.gate_dev = torch.zeros(2, dtype=torch.int32, device=dev)
             self.skipped_dev = torch.zeros(2, dtype=torch.int64, device=dev)        # (the kernel's uint64 pair: same bits)
+        # the path is fixed by now (step): behind the gate | the norm beside the update | the norm ahead of it (clipped, or not fused)
+        fused = dev.type == 'cuda' and FUSED_OPT_NORM
+        self._features = ((_rn.OPT_F_GATE if self.skip_nonfinite else _rn.OPT_F_NORM if fused and self.clip <= 0.0 else 0)
+                          | (_rn.OPT_F_CLIP if self.clip > 0.0 else 0)
+                          | (_rn.OPT_F_LRDEV if fused and self.lr_dev is not None else 0)   # (not fused: the host evaluates the schedule)
+                          | (_rn.OPT_F_EMA if self.ema is not None else 0) | (_rn.OPT_F_ACCUM if self.acc is not None else 0))
         self.step_count = 0
+
+    def _update(self, lo, hi, grad_scale, advance_counter, partial=None, stream=None, lr=None, step=None):
+        """rn_optimizer_update over [lo, hi) of the arena with this optimizer's features; only the fields of set features are filled.
+        `lr` / `step` default to the base rate and the 1-based number of the update begin_step counted (Adam's bias correction):
+        both are read only without RN_OPT_F_LRDEV."""
+        a, f = self.arena, self._features
+        u = _rn.OptUpdate(kind=_rn.OPT[self.kind], features=f, w=a.weights[lo:].data_ptr(), grad=a.grads[lo:].data_ptr(),
+                          state1=self.state1[lo:].data_ptr(), state2=self.state2[lo:].data_ptr() if self.state2 is not None else None,
+                          wd_per_block=a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), count=hi - lo,
+                          lr=self.lr if lr is None else lr, grad_scale=grad_scale, step=self._update_no if step is None else step,
+                          advance_counter=advance_counter.data_ptr() if advance_counter is not None else None,
+                          advance_by=ops.DROPOUT_COUNTER_STEP)
+        if f & _rn.OPT_F_NORM:
+            u.partial = partial.data_ptr()
+        if f & _rn.OPT_F_LRDEV:
+            u.lr_dev = _rn.f32(self.lr_dev)
+        if f & _rn.OPT_F_EMA:
+            u.ema, u.ema_dev = self.ema[lo:].data_ptr(), _rn.f32(self.ema_dev)
+        if f & _rn.OPT_F_CLIP:
+            u.clip_norm, u.norm_sq = self.clip, _rn.f32(self.norm_reg)
+        if f & _rn.OPT_F_ACCUM:
+            u.acc, u.inv_accum, u.accum_dev = self.acc[lo:].data_ptr(), 1.0 / self.accumulate_steps, self.accum_dev.data_ptr()
+        if f & _rn.OPT_F_GATE:
+            u.gate_dev = self.gate_dev.data_ptr()
+        _rn.check(_rn.lib().rn_optimizer_update(ctypes.byref(u), stream if stream is not None else _rn.stream()), 'rn_optimizer_update')
 
     def count_step(self):
         """The host's side of one (micro-)step: step_count counts UPDATES, so with accumulate_steps = A it moves on every A-th call.
@@ -317,22 +349,7 @@ class Optimizer(object):
         if self.ema is not None:
             _rn.check(L_.rn_ema_decay_eval(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(), _rn.f32(self.ema_dev),
                                            _rn.stream()), 'rn_ema_decay_eval')
-            _rn.check(L_.rn_optimizer_step_ema(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
-                                               _rn.f32(self.state2) if self.state2 is not None else None,
-                                               _rn.f32(a.wd_per_block), a.count, lr, None, grad_scale, self.clip,
-                                               _rn.f32(self.norm_reg), self.step_count,
-                                               advance_counter.data_ptr() if advance_counter is not None else None,
-                                               ops.DROPOUT_COUNTER_STEP, None, _rn.f32(self.ema), _rn.f32(self.ema_dev), _rn.stream()),
-                      'rn_optimizer_step_ema')
-            import ops_f16
-            ops_f16.weights_changed()
-            return
-        _rn.check(L_.rn_optimizer_step(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
-                                       _rn.f32(self.state2) if self.state2 is not None else None,
-                                       _rn.f32(a.wd_per_block), a.count, lr, grad_scale, self.clip,
-                                       _rn.f32(self.norm_reg), self.step_count,
-                                       advance_counter.data_ptr() if advance_counter is not None else None,
-                                       ops.DROPOUT_COUNTER_STEP, _rn.stream()), 'rn_optimizer_step')
+        self._update(0, a.count, grad_scale, advance_counter, lr=lr, step=self.step_count)
         import ops_f16
         ops_f16.weights_changed()      # fp16-packed copies of the kernels (inference path) are stale now
 
@@ -350,16 +367,7 @@ class Optimizer(object):
                                           self._partial.data_ptr(), _rn.stream()), 'rn_grad_norm_partial')
         _rn.check(L_.rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),
                   'rn_norm_reg_finalize')
-        _rn.check(L_.rn_optimizer_step_clip(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
-                                            _rn.f32(self.state2) if self.state2 is not None else None,
-                                            _rn.f32(a.wd_per_block), a.count, self.lr,
-                                            _rn.f32(self.lr_dev) if self.lr_dev is not None else None, grad_scale, self.clip,
-                                            _rn.f32(self.norm_reg), self._update_no,
-                                            advance_counter.data_ptr() if advance_counter is not None else None,
-                                            ops.DROPOUT_COUNTER_STEP,
-                                            _rn.f32(self.ema) if self.ema is not None else None,
-                                            _rn.f32(self.ema_dev) if self.ema is not None else None, _rn.stream()),
-                  'rn_optimizer_step_clip')
+        self._update(0, a.count, grad_scale, advance_counter)
         import ops_f16
         ops_f16.weights_changed()
 
@@ -386,16 +394,7 @@ class Optimizer(object):
         if self.ema is not None:
             _rn.check(L_.rn_ema_decay_eval_gated(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(),
                                                  _rn.f32(self.ema_dev), self.gate_dev.data_ptr(), _rn.stream()), 'rn_ema_decay_eval_gated')
-        _rn.check(L_.rn_optimizer_step_gated(_rn.OPT[self.kind], _rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(self.state1),
-                                             _rn.f32(self.state2) if self.state2 is not None else None,
-                                             _rn.f32(a.wd_per_block), a.count, self.lr,
-                                             _rn.f32(self.lr_dev) if self.lr_dev is not None else None, grad_scale, self.clip,
-                                             _rn.f32(self.norm_reg), 1,
-                                             advance_counter.data_ptr() if advance_counter is not None else None,
-                                             ops.DROPOUT_COUNTER_STEP,
-                                             _rn.f32(self.ema) if self.ema is not None else None,
-                                             _rn.f32(self.ema_dev) if self.ema is not None else None,
-                                             self.gate_dev.data_ptr(), _rn.stream()), 'rn_optimizer_step_gated')
+        self._update(0, a.count, grad_scale, advance_counter, step=1)
         import ops_f16
         ops_f16.weights_changed()
 
@@ -458,6 +457,7 @@ class Optimizer(object):
     def step_slice(self, lo, hi, grad_scale, advance_counter=None, stream=None):
         a, L_ = self.arena, _rn.lib()
         assert 0 <= lo < hi <= a.count and lo % OPT_BLOCK == 0 and hi % OPT_BLOCK == 0
+        assert self._features & _rn.OPT_F_NORM, "slices form the norm beside the update: not with clipping or the guard"
         npairs = int(L_.rn_optimizer_norm_pairs(hi - lo))
         assert 2 * (self._pairs + npairs) <= self._partial.numel()
         part = self._partial[2 * self._pairs:]
@@ -467,43 +467,7 @@ class Optimizer(object):
             other = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(getattr(stream, 'value', stream)))
             other.wait_event(self._sched_event)
             stream = ctypes.c_void_p(other.cuda_stream)
-        if self.acc is not None:
-            _rn.check(L_.rn_optimizer_step_accum(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(),
-                                                 self.acc[lo:].data_ptr(), self.state1[lo:].data_ptr(),
-                                                 self.state2[lo:].data_ptr() if self.state2 is not None else None,
-                                                 a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), hi - lo, self.lr,
-                                                 _rn.f32(self.lr_dev) if self.lr_dev is not None else None, grad_scale,
-                                                 1.0 / self.accumulate_steps, self.accum_dev.data_ptr(), self._update_no,
-                                                 advance_counter.data_ptr() if advance_counter is not None else None,
-                                                 ops.DROPOUT_COUNTER_STEP, part.data_ptr(),
-                                                 self.ema[lo:].data_ptr() if self.ema is not None else None,
-                                                 _rn.f32(self.ema_dev) if self.ema is not None else None,
-                                                 stream if stream is not None else _rn.stream()), 'rn_optimizer_step_accum')
-            return
-        if self.ema is not None:
-            _rn.check(L_.rn_optimizer_step_ema(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(),
-                                               self.state1[lo:].data_ptr(),
-                                               self.state2[lo:].data_ptr() if self.state2 is not None else None,
-                                               a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), hi - lo, self.lr,
-                                               _rn.f32(self.lr_dev) if self.lr_dev is not None else None, grad_scale, 0.0, None,
-                                               self.step_count, advance_counter.data_ptr() if advance_counter is not None else None,
-                                               ops.DROPOUT_COUNTER_STEP, part.data_ptr(), self.ema[lo:].data_ptr(), _rn.f32(self.ema_dev),
-                                               stream if stream is not None else _rn.stream()), 'rn_optimizer_step_ema')
-            return
-        if self.lr_dev is not None:
-            _rn.check(L_.rn_optimizer_step_norm_lrdev(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(),
-                                                      self.state1[lo:].data_ptr(),
-                                                      self.state2[lo:].data_ptr() if self.state2 is not None else None,
-                                                      a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), hi - lo, _rn.f32(self.lr_dev), grad_scale,
-                                                      advance_counter.data_ptr() if advance_counter is not None else None,
-                                                      ops.DROPOUT_COUNTER_STEP, part.data_ptr(),
-                                                      stream if stream is not None else _rn.stream()), 'rn_optimizer_step_norm_lrdev')
-            return
-        _rn.check(L_.rn_optimizer_step_norm(_rn.OPT[self.kind], a.weights[lo:].data_ptr(), a.grads[lo:].data_ptr(), self.state1[lo:].data_ptr(),
-                                            self.state2[lo:].data_ptr() if self.state2 is not None else None,
-                                            a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), hi - lo, self.lr, grad_scale, self.step_count,
-                                            advance_counter.data_ptr() if advance_counter is not None else None, ops.DROPOUT_COUNTER_STEP,
-                                            part.data_ptr(), stream if stream is not None else _rn.stream()), 'rn_optimizer_step_norm')
+        self._update(lo, hi, grad_scale, advance_counter, partial=part, stream=stream)
 
     def finish_step(self):
         _rn.check(_rn.lib().rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),

@@ -13,7 +13,7 @@ import step_tail_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("momentum", "rmsprop", "adam")
-NEW_SYMBOLS = ("rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated", "rn_optimizer_step_accum")
+NEW_SYMBOLS = ("rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated", "rn_optimizer_update")
 
 
 def _same(a, b):
@@ -117,8 +117,10 @@ def test_entries_refuse_bad_arguments_without_a_launch():
     assert L.rn_ema_decay_eval_gated(1.0, 1, word, two, pair, None) != 0
 
     def step(acc=base, accum_dev=pair, partial=part, count=1024, inv=0.5, ema=None, ema_dev=None, state2=None, kind=0):
-        return L.rn_optimizer_step_accum(kind, base, base, acc, base, state2, two, count, 0.1, None, 1.0, inv, accum_dev, 1, None, 0,
-                                         partial, ema, ema_dev, None)
+        f = _rn.OPT_F_NORM | _rn.OPT_F_ACCUM | (_rn.OPT_F_EMA if None not in (ema, ema_dev) else 0)
+        u = _rn.OptUpdate(kind=kind, features=f, w=base, grad=base, state1=base, state2=state2, wd_per_block=two, count=count, lr=0.1,
+                          grad_scale=1.0, step=1, partial=partial, ema=ema, ema_dev=ema_dev, acc=acc, inv_accum=inv, accum_dev=accum_dev)
+        return L.rn_optimizer_update(ctypes.byref(u), None)
     assert step(acc=None) != 0 and step(accum_dev=None) != 0 and step(partial=None) != 0
     assert step(acc=base + 4) != 0                                                   # not 16-byte aligned
     assert b"16-byte" in L.rn_last_error()

@@ -14,7 +14,7 @@ import step_tail_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("momentum", "rmsprop", "adam")
-NEW_SYMBOLS = ("rn_optimizer_step_clip", "rn_grad_norm_partial")
+NEW_SYMBOLS = ("rn_optimizer_update", "rn_grad_norm_partial")
 
 
 def _same(a, b):
@@ -108,8 +108,10 @@ def test_entries_refuse_bad_arguments_without_a_launch():
     q, odd = ctypes.c_void_p(4096), ctypes.c_void_p(4096 + 4)
 
     def clip(kind=0, state2=None, count=1024, lr_dev=None, clip_norm=0.5, norm_sq=q, step=1, ema=None, ema_dev=None, w=q):
-        return L.rn_optimizer_step_clip(kind, w, q, q, state2, q, count, 0.1, lr_dev, 1.0, clip_norm, norm_sq, step, None, 0, ema,
-                                        ema_dev, None)
+        f = _rn.OPT_F_CLIP | (_rn.OPT_F_LRDEV if lr_dev is not None else 0) | (_rn.OPT_F_EMA if None not in (ema, ema_dev) else 0)
+        u = _rn.OptUpdate(kind=kind, features=f, w=w, grad=q, state1=q, state2=state2, wd_per_block=q, count=count, lr=0.1,
+                          grad_scale=1.0, step=step, lr_dev=lr_dev, ema=ema, ema_dev=ema_dev, clip_norm=clip_norm, norm_sq=norm_sq)
+        return L.rn_optimizer_update(ctypes.byref(u), None)
     for c in (0.0, -1.0, float("nan")):
         assert clip(clip_norm=c) == -1
         assert b"clip_norm" in L.rn_last_error()

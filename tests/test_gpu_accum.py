@@ -218,7 +218,7 @@ def test_small_arena_accumulates_scheduled_adam(dev, A):
 @pytest.mark.parametrize("kind", KINDS)
 def test_exact_sums_equal_a_plain_update_on_the_means(dev, kind, A):
     """No L2, grad_scale 1, gradients k / 64 in [-1024, 1024]: every sum and the division by A are exact in float32, so after each
-    update w, the slots and norm_reg equal, bit for bit, what rn_optimizer_step_norm leaves when it is given the exact means."""
+    update w, the slots and norm_reg equal, bit for bit, what the update without RN_OPT_F_ACCUM leaves when it is given the exact means."""
     inp = ref.exact_case(A)
     got = _run(dev, inp, kind, A)
     means = tuple(m.astype(np.float32) for m in ref.cycle_means(inp, A))

@@ -1,5 +1,5 @@
 """Global-norm clipping inside the one-graph training step, on the MI355X (-m gpu): the clipped update that reads norm, rate and
-decay from the device (rn_grad_norm_partial + rn_norm_reg_finalize + rn_optimizer_step_clip) against the float64 reference
+decay from the device (rn_grad_norm_partial + rn_norm_reg_finalize + rn_optimizer_update under RN_OPT_F_CLIP) against the float64 reference
 (clip_ref.py), a loose clip against the unclipped fused path bit for bit, the slice entry of the norm pass, Optimizer.step()
 captured and replayed by itself, and a clipped trainer's ONE captured graph against eager launches, against one graph per part,
 the reference, a checkpoint and the command line.
@@ -147,7 +147,7 @@ def test_small_arena_against_the_reference(dev, kind, clip, scheduled, setting):
 @pytest.mark.parametrize("kind", KINDS)
 def test_loose_clip_equals_the_unclipped_fused_path(dev, kind, scheduled, setting):
     """clip / max(norm, clip) is exactly 1 under CLIP_LOOSE: w, the slots and the average equal, bit for bit, what the unclipped
-    path (rn_optimizer_step_norm and its kin, the norm formed beside the update) leaves; norm_reg, summed in another order by
+    path (RN_OPT_F_NORM, the norm formed beside the update) leaves; norm_reg, summed in another order by
     another kernel, agrees within TOL."""
     inp = ref.clip_case("small")
     loose = _run(dev, inp, kind, ref.CLIP_LOOSE, scheduled, setting)

@@ -2,6 +2,7 @@
 update kernel keeps against the float64 reference (ema_ref.py) on the synthetic arenas of test_gpu_step_tail.py, an EMA trainer's
 ONE captured graph against eager launches and across a checkpoint, Trainer.ema_weights(), and the command line."""
 import collections
+import ctypes
 import functools
 import os
 
@@ -75,11 +76,14 @@ def test_entries_refuse_bad_arguments(dev):
     assert int(word.item()) == 0 and not ema_dev.cpu().numpy().any()          # nothing was launched
     w = torch.zeros(1024, dtype=torch.float32, device=dev)
     wd = torch.zeros(1, dtype=torch.float32, device=dev)
-    args = lambda e, ed: (0, _rn.f32(w), _rn.f32(w), _rn.f32(w), None, _rn.f32(wd), 1024, 0.1, None, 1.0, 0.0, None, 1, None, 0, None,
-                          e, ed, _rn.stream())
-    assert L.rn_optimizer_step_ema(*args(None, _rn.f32(ema_dev))) != 0
-    assert L.rn_optimizer_step_ema(*args(_rn.f32(w), None)) != 0
-    assert L.rn_optimizer_step_ema(*args(w[1:].data_ptr(), _rn.f32(ema_dev))) != 0      # not 16-byte aligned
+
+    def step_ema(e, ed):
+        u = _rn.OptUpdate(kind=0, features=_rn.OPT_F_EMA, w=_rn.f32(w), grad=_rn.f32(w), state1=_rn.f32(w), wd_per_block=_rn.f32(wd),
+                          count=1024, lr=0.1, grad_scale=1.0, step=1, ema=e, ema_dev=ed)
+        return L.rn_optimizer_update(ctypes.byref(u), _rn.stream())
+    assert step_ema(None, _rn.f32(ema_dev)) != 0
+    assert step_ema(_rn.f32(w), None) != 0
+    assert step_ema(w[1:].data_ptr(), _rn.f32(ema_dev)) != 0      # not 16-byte aligned
     torch.cuda.synchronize()
 
 
@@ -191,7 +195,7 @@ def test_small_arena_average(dev, kind, setting):
 @pytest.mark.parametrize("setting", SETTINGS)
 @pytest.mark.parametrize("kind", ["momentum", "adam"])
 def test_small_arena_average_with_clipping(dev, kind, setting):
-    """rn_grad_norm_l2reg + rn_optimizer_step_ema with clipping: clip 0.5 binds, clip 1e6 does not -- then e equals the fused
+    """The norm pass + rn_optimizer_update (CLIP + EMA): clip 0.5 binds, clip 1e6 does not -- then e equals the fused
     path's bit for bit.  w and the slots equal a clipped run's without the average bit for bit."""
     inp = ref.ema_case("small")
     binds = _run(dev, inp, kind, setting, clip=step_tail_ref.CLIP_BINDS)

@@ -283,10 +283,19 @@ def test_entries_called_directly(dev):
     counter = torch.zeros(1, dtype=torch.int64, device=dev)
     w0 = w.clone()
 
+    def gated(kind, w, grad, state1, state2, wd, count, lr, lr_dev, grad_scale, clip_norm, norm_sq, step, advance_counter, advance_by,
+              ema, ema_dev, gate_dev, stream):
+        f = (_rn.OPT_F_GATE | (_rn.OPT_F_CLIP if clip_norm > 0 else 0) | (_rn.OPT_F_LRDEV if lr_dev is not None else 0)
+             | (_rn.OPT_F_EMA if None not in (ema, ema_dev) else 0))
+        u = _rn.OptUpdate(kind=kind, features=f, w=w, grad=grad, state1=state1, state2=state2, wd_per_block=wd, count=count, lr=lr,
+                          grad_scale=grad_scale, step=step, advance_counter=advance_counter, advance_by=advance_by, lr_dev=lr_dev,
+                          ema=ema, ema_dev=ema_dev, clip_norm=clip_norm, norm_sq=norm_sq, gate_dev=gate_dev)
+        return L.rn_optimizer_update(ctypes.byref(u), stream)
+
     def update(g):
         gate[1] = g
-        _rn.check(L.rn_optimizer_step_gated(0, _rn.f32(w), _rn.f32(grad), _rn.f32(s1), None, _rn.f32(wd), n, 0.5, None, 1.0, 0.0, None, 1,
-                                            counter.data_ptr(), 3, None, None, gate.data_ptr(), _rn.stream()), "rn_optimizer_step_gated")
+        _rn.check(gated(0, _rn.f32(w), _rn.f32(grad), _rn.f32(s1), None, _rn.f32(wd), n, 0.5, None, 1.0, 0.0, None, 1,
+                        counter.data_ptr(), 3, None, None, gate.data_ptr(), _rn.stream()), "rn_optimizer_update")
         torch.cuda.synchronize()
     update(0)
     assert torch.equal(w, w0) and not s1.any() and counter.item() == 3
@@ -297,11 +306,11 @@ def test_entries_called_directly(dev):
     assert L.rn_finite_gate_eval(None, q, q, None) < 0 and L.rn_finite_gate_eval(q, None, q, None) < 0 and L.rn_finite_gate_eval(q, q, None, None) < 0
     assert L.rn_finite_gate_eval(q, ctypes.c_void_p(norm.data_ptr() + 2), q, None) < 0
     args = [0, _rn.f32(w), _rn.f32(grad), _rn.f32(s1), None, _rn.f32(wd), n, 0.5, None, 1.0, 0.0, None, 1, None, 0, None, None]
-    assert L.rn_optimizer_step_gated(*(args + [None, None])) < 0
-    assert L.rn_optimizer_step_gated(*(args[:10] + [-1.0] + args[11:] + [gate.data_ptr(), None])) < 0
-    assert L.rn_optimizer_step_gated(*(args[:10] + [0.5] + args[11:] + [gate.data_ptr(), None])) < 0          # clipping without norm_sq
-    assert L.rn_optimizer_step_gated(*(args[:6] + [n - 24] + args[7:] + [gate.data_ptr(), None])) < 0
-    assert L.rn_optimizer_step_gated(*([2] + args[1:] + [gate.data_ptr(), None])) < 0                         # Adam without state2
+    assert gated(*(args + [None, None])) < 0
+    assert gated(*(args[:10] + [-1.0] + args[11:] + [gate.data_ptr(), None])) < 0
+    assert gated(*(args[:10] + [0.5] + args[11:] + [gate.data_ptr(), None])) < 0          # clipping without norm_sq
+    assert gated(*(args[:6] + [n - 24] + args[7:] + [gate.data_ptr(), None])) < 0
+    assert gated(*([2] + args[1:] + [gate.data_ptr(), None])) < 0                         # Adam without state2
     torch.cuda.synchronize()
     assert torch.equal(w, w0 - 0.5 * grad)
 

@@ -273,7 +273,7 @@ def _check_optimizer(inp, kind, got, want, tag):
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_optimizer_small_arena_fused_norm(dev, kind):
-    """grad_clip_norm=None: rn_optimizer_step_norm + rn_norm_reg_finalize, whole and in three slices at non-zero offsets.
+    """grad_clip_norm=None: rn_optimizer_update (RN_OPT_F_NORM) + rn_norm_reg_finalize, whole and in three slices at non-zero offsets.
     Parameters of 1152, 700, 1, 1025 and 3000 elements with l2 scales 0.3, 0.05, 1.0, none and 0.6: a wrong block index, or
     a decay that is dropped, moves the weights by far more than TOL."""
     inp = ref.optimizer_case("small")
@@ -288,7 +288,7 @@ def test_optimizer_small_arena_fused_norm(dev, kind):
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_optimizer_small_arena_clipping(dev, kind):
-    """rn_grad_norm_l2reg + rn_optimizer_step.  Clip 0.5 binds (the norm is about 100).  Clip 1e6 does not: clip / max(norm,
+    """The norm pass + rn_optimizer_update (RN_OPT_F_CLIP).  Clip 0.5 binds (the norm is about 100).  Clip 1e6 does not: clip / max(norm,
     clip) is exactly 1, so the weights equal the unclipped run's bit for bit and norm_reg agrees with the fused path's."""
     inp = ref.optimizer_case("small")
     binds = _run_optimizer(dev, inp, kind, clip=ref.CLIP_BINDS)

@@ -15,7 +15,7 @@ import step_tail_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("momentum", "rmsprop", "adam")
-NEW_SYMBOLS = ("rn_finite_gate_eval", "rn_optimizer_step_gated")
+NEW_SYMBOLS = ("rn_finite_gate_eval", "rn_optimizer_update")
 FLT_MAX = float(np.finfo(np.float32).max)
 
 
@@ -167,7 +167,7 @@ def test_the_guard_is_part_of_the_graph_key_and_adds_no_condition():
     guarded = inspect.getsource(train.Optimizer._step_guarded)
     assert "begin_step" not in guarded.replace("begin_step's", "") and "rn_lr_schedule_eval(" not in guarded and "rn_ema_decay_eval(" not in guarded
     order = [guarded.index(s) for s in ("L_.rn_grad_norm_partial(", "L_.rn_norm_reg_finalize(", "L_.rn_finite_gate_eval(",
-                                        "L_.rn_lr_schedule_eval_gated(", "L_.rn_ema_decay_eval_gated(", "L_.rn_optimizer_step_gated(")]
+                                        "L_.rn_lr_schedule_eval_gated(", "L_.rn_ema_decay_eval_gated(", "self._update(0, a.count, grad_scale, advance_counter, step=1)")]
     assert order == sorted(order)
 
 
@@ -197,8 +197,12 @@ def test_entries_refuse_bad_arguments_without_a_launch():
     assert gate(gate_dev=odd2) == -1 and gate(skipped=odd4) == -1 and b"misaligned" in L.rn_last_error()
 
     def step(kind=0, state2=None, count=1024, lr_dev=None, clip_norm=0.0, norm_sq=None, step=1, ema=None, ema_dev=None, w=q, gate_dev=q):
-        return L.rn_optimizer_step_gated(kind, w, q, q, state2, q, count, 0.1, lr_dev, 1.0, clip_norm, norm_sq, step, None, 0, ema,
-                                         ema_dev, gate_dev, None)
+        f = (_rn.OPT_F_GATE | (_rn.OPT_F_CLIP if clip_norm > 0 else 0) | (_rn.OPT_F_LRDEV if lr_dev is not None else 0)
+             | (_rn.OPT_F_EMA if None not in (ema, ema_dev) else 0))
+        u = _rn.OptUpdate(kind=kind, features=f, w=w, grad=q, state1=q, state2=state2, wd_per_block=q, count=count, lr=0.1,
+                          grad_scale=1.0, step=step, lr_dev=lr_dev, ema=ema, ema_dev=ema_dev, clip_norm=clip_norm, norm_sq=norm_sq,
+                          gate_dev=gate_dev)
+        return L.rn_optimizer_update(ctypes.byref(u), None)
     assert step(gate_dev=None) == -1 and b"gate_dev" in L.rn_last_error()
     assert step(gate_dev=odd2) == -1 and b"aligned" in L.rn_last_error()
     for c in (-1.0, float("nan")):

@@ -119,7 +119,7 @@ def test_default_total_steps_at_or_below_the_warmup_is_refused():
 
 
 def test_c_entry_checks_its_arguments_before_any_launch():
-    """rn_lr_schedule_eval / rn_optimizer_step_norm_lrdev: a bad descriptor is RN_EINVAL with a message (no device here; 8 stands
+    """rn_lr_schedule_eval / rn_optimizer_update (NORM + LRDEV): a bad descriptor is RN_EINVAL with a message (no device here; 8 stands
     for "some non-null pointer")."""
     import _rn
     L = _rn.lib()
@@ -147,8 +147,14 @@ def test_c_entry_checks_its_arguments_before_any_launch():
     assert call("step", boundaries=(7, 7)) == -1 and b"increasing" in L.rn_last_error()
     assert call("step", boundaries=(7, 4)) == -1 and call("step", boundaries=(-1, 4)) == -1
     q = ctypes.c_void_p(4096)
-    assert L.rn_optimizer_step_norm_lrdev(0, q, q, q, None, q, 1024, None, 1.0, None, 0, q, None) == -1
+
+    def norm_lrdev(kind, w, grad, state1, state2, wd, count, lr_dev, grad_scale, advance_counter, advance_by, partial, stream):
+        u = _rn.OptUpdate(kind=kind, features=_rn.OPT_F_NORM | _rn.OPT_F_LRDEV, w=w, grad=grad, state1=state1, state2=state2,
+                          wd_per_block=wd, count=count, grad_scale=grad_scale, advance_counter=advance_counter,
+                          advance_by=advance_by, partial=partial, lr_dev=lr_dev)
+        return L.rn_optimizer_update(ctypes.byref(u), stream)
+    assert norm_lrdev(0, q, q, q, None, q, 1024, None, 1.0, None, 0, q, None) == -1
     assert b"device rate" in L.rn_last_error()
-    assert L.rn_optimizer_step_norm_lrdev(0, q, q, q, None, q, 1024, q, 1.0, None, 0, None, None) == -1
-    assert L.rn_optimizer_step_norm_lrdev(2, q, q, q, None, q, 1024, q, 1.0, None, 0, q, None) == -1    # adam needs state2
-    assert L.rn_optimizer_step_norm_lrdev(0, q, q, q, None, q, 1000, q, 1.0, None, 0, q, None) == -1    # not whole blocks
+    assert norm_lrdev(0, q, q, q, None, q, 1024, q, 1.0, None, 0, None, None) == -1
+    assert norm_lrdev(2, q, q, q, None, q, 1024, q, 1.0, None, 0, q, None) == -1    # adam needs state2
+    assert norm_lrdev(0, q, q, q, None, q, 1000, q, 1.0, None, 0, q, None) == -1    # not whole blocks

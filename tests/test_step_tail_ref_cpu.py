@@ -193,3 +193,47 @@ def test_optimizer_inputs_reach_the_edges(name):
         assert inp.sizes[0] == 2097152 + 5 * 1024 + 7 and all(o >= 2097152 for o in inp.offsets[1:])
         assert all(s is not None for s in inp.l2)
 
+
+
+def test_update_descriptor_refuses_features_and_fields_that_do_not_agree():
+    """rn_optimizer_update picks its kernel from `features`, and a field that does not agree with them is refused with RN_EINVAL
+    (-1) and a message ahead of any launch: fake non-null pointers that are never dereferenced, no device needed."""
+    import ctypes
+    import _rn
+    L = _rn.lib()
+    q = ctypes.c_void_p(4096)
+    N, CLIP, A, G = _rn.OPT_F_NORM, _rn.OPT_F_CLIP, _rn.OPT_F_ACCUM, _rn.OPT_F_GATE
+    fields = {N: dict(partial=q), CLIP: dict(clip_norm=0.5, norm_sq=q), A: dict(acc=q, inv_accum=0.5, accum_dev=q), G: dict(gate_dev=q)}
+
+    def update(features, **over):
+        """Every field of every set feature is filled as the header asks, then `over`: only the combination can be at fault."""
+        kw = dict(kind=0, features=features, w=q, grad=q, state1=q, wd_per_block=q, count=1024, lr=0.1, grad_scale=1.0, step=1)
+        for bit, f in fields.items():
+            if features & bit:
+                kw.update(f)
+        kw.update(over)
+        u = _rn.OptUpdate(**kw)
+        return L.rn_optimizer_update(ctypes.byref(u), None), L.rn_last_error()
+
+    rc = L.rn_optimizer_update(None, None)
+    assert rc == -1 and b"descriptor" in L.rn_last_error()
+    for bad in (64, 1 << 31, N | 128):
+        rc, msg = update(bad)
+        assert rc == -1 and b"feature bit" in msg, bad
+    for features, word in ((N | CLIP, b"NORM"), (G | N, b"NORM"), (G | A, b"ACCUM"), (A, b"ACCUM"), (N | A | CLIP, b"CLIP"),
+                           (N | A | G, b"GATE")):
+        rc, msg = update(features)
+        assert rc == -1 and word in msg and b"neither" in msg, (features, msg)
+    # a field of a feature that is clear: a pointer set by mistake does not pass, and does not select a kernel
+    rc, msg = update(0, partial=q)
+    assert rc == -1 and b"partial" in msg
+    rc, msg = update(0, gate_dev=q)
+    assert rc == -1 and b"gate_dev" in msg
+    rc, msg = update(0, clip_norm=-1.0)
+    assert rc == -1 and b"clip_norm" in msg
+    rc, msg = update(0, norm_sq=q)
+    assert rc == -1 and b"norm_sq" in msg
+    rc, msg = update(0, lr_dev=q)
+    assert rc == -1 and b"device rate" in msg
+    rc, msg = update(N, acc=q, accum_dev=q, inv_accum=0.5)
+    assert rc == -1 and b"ACCUM" in msg
