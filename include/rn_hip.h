@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 416
+#define RN_API_VERSION 417
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -704,6 +704,33 @@ int rn_conv3x3_winograd_gn_bwd(const rn_conv_seg* segs, int nseg, int cin, int c
  * (untouched since), v_buf and the same urot_buf-was-given flag; dw (+)= as `accumulate` says. */
 int rn_conv3x3_winograd_gn_bwd_wgrad(const rn_conv_seg* segs, int nseg, int cin, int cout, float* dw, int accumulate, int tile,
                                      void* workspace, size_t workspace_bytes, const float* v_buf, int urot_was_given, rn_stream_t stream);
+/* Which kernels one layer's rn_conv3x3_winograd_gn ("fwd") and rn_conv3x3_winograd_gn_bwd ("bwd") calls launch, decided by the
+ * planner the launches use (the same functions, the same constants, RN_WINO_GN_W / RN_WINO_W and the product switches read at
+ * the call) -- for tests that must know which branch a shape takes.  Host only: touches no device, launches nothing; of the
+ * segments only n, h, w are read.  in_groups / out_groups: the groups of the folded GroupNorm on the input / output side
+ * (rn_wino_gn.in_groups / out_groups), 0: that side is not folded (in_rows / out_rows NULL).
+ * A call has an input side (fwd: x, cin channels; bwd: dy, cout channels) and an output side (fwd: y, cout; bwd: dx, cin).
+ * The CHUNK kernels (a block = 16 tiles of one sample x 16 lanes of W channels; `slabs` blocks side by side cover the
+ * channels) run every folded side, the fwd input side and the bwd output side; a side that is not folded otherwise runs the
+ * GRID-STRIDE kernels of rn_conv3x3_winograd (the fwd output transform of a layer that emits no rows, the dy transforms of
+ * plain dy).  A chunk kernel on a folded side reads its sample's statistic rows: staged in LDS while groups per block x
+ * chunks per sample <= 1024, from global memory otherwise. */
+typedef struct rn_wino_gn_plan_call {
+  int32_t in_chunked, out_chunked;  /* 1: chunk kernel, 0: grid-stride kernel */
+  int32_t in_w, out_w;              /* channels per thread (1, 2, 4) of the side's chunk kernel; 0: not chunked */
+  int32_t in_slabs, out_slabs;      /* channels / (16 W) of the side's chunk kernel; 0: not chunked */
+  int32_t stride_w;                 /* channels per thread (1, 2, 4) of the call's grid-stride kernel; 0: it launches none */
+  int32_t in_staged, out_staged;    /* 1: every segment's rows staged in LDS, 0: some segment reads them from global memory,
+                                       -1: the side reads no rows (not folded; fwd output side: it writes them) */
+} rn_wino_gn_plan_call;
+typedef struct rn_wino_gn_plan {
+  rn_wino_gn_plan_call fwd, bwd;
+  int32_t tiles, chunks;            /* Winograd tiles and chunks (= statistic rows, rn_wino_gn_rows) of all segments */
+  int32_t partial_chunk;            /* 1: some segment's tiles per sample are no multiple of 16 (its last chunk is partly empty) */
+  int32_t u_frag;                   /* 1: the forward product reads U as the fragment image (rn_x3_bfrag_ok), 0: as fp32 */
+} rn_wino_gn_plan;
+int rn_conv3x3_winograd_gn_plan(const rn_conv_seg* segs, int nseg, int cin, int cout, int tile, int in_groups, int out_groups,
+                                rn_wino_gn_plan* plan);
 /* out[i] = (accumulate ? out[i] : 0) + sum_r in[r * count + i], r < nrows, fixed order (bit-reproducible); joins the
  * caller's deferred batch when `defer` is given.  Finishes dgamma / dbeta from in_g_rows_chan. */
 int rn_reduce_rows(const float* in, float* out, int64_t count, int nrows, int accumulate, rn_stream_t stream, rn_reduce_list* defer);

@@ -21,7 +21,7 @@ OPT_BLOCK = 1024
 LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
-API_VERSION = 416        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 417        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -73,6 +73,19 @@ class WinoGnBwd(C.Structure):
                 ("in_act", C.c_int32), ("in_eps", C.c_float), ("in_g_rows_group", C.c_void_p), ("in_g_rows_chan", C.c_void_p),
                 ("out_rows", C.c_void_p), ("out_g_rows_group", C.c_void_p), ("out_gamma", C.c_void_p),
                 ("out_groups", C.c_int32), ("out_eps", C.c_float), ("defer_wgrad", C.c_int32)]
+
+
+class WinoGnPlanCall(C.Structure):
+    """rn_wino_gn_plan_call"""
+    _fields_ = [("in_chunked", C.c_int32), ("out_chunked", C.c_int32), ("in_w", C.c_int32), ("out_w", C.c_int32),
+                ("in_slabs", C.c_int32), ("out_slabs", C.c_int32), ("stride_w", C.c_int32), ("in_staged", C.c_int32),
+                ("out_staged", C.c_int32)]
+
+
+class WinoGnPlan(C.Structure):
+    """rn_wino_gn_plan: the kernels one folded Winograd layer launches (rn_conv3x3_winograd_gn_plan, host only)"""
+    _fields_ = [("fwd", WinoGnPlanCall), ("bwd", WinoGnPlanCall), ("tiles", C.c_int32), ("chunks", C.c_int32),
+                ("partial_chunk", C.c_int32), ("u_frag", C.c_int32)]
 
 
 class ReduceDesc(C.Structure):
@@ -203,7 +216,7 @@ SYMBOLS = [
     "rn_conv2d_bias_grad_workspace", "rn_conv2d_bias_grad", "rn_conv3x3_winograd_workspace", "rn_conv3x3_winograd",
     "rn_conv3x3_winograd_wgrad_workspace", "rn_conv3x3_winograd_wgrad", "rn_conv3x3_winograd_keep_bytes",
     "rn_conv3x3_winograd_bwd_workspace", "rn_conv3x3_winograd_bwd", "rn_flush_reductions", "rn_gemm_batched",
-    "rn_winograd_bwd_products_workspace", "rn_winograd_bwd_products", "rn_wino_gn_rows", "rn_conv3x3_winograd_gn", "rn_conv3x3_winograd_gn_bwd", "rn_conv3x3_winograd_gn_bwd_wgrad", "rn_reduce_rows", "rn_resize_bilinear_normalize", "rn_resize_pair_u8",
+    "rn_winograd_bwd_products_workspace", "rn_winograd_bwd_products", "rn_wino_gn_rows", "rn_conv3x3_winograd_gn", "rn_conv3x3_winograd_gn_bwd", "rn_conv3x3_winograd_gn_bwd_wgrad", "rn_conv3x3_winograd_gn_plan", "rn_reduce_rows", "rn_resize_bilinear_normalize", "rn_resize_pair_u8",
     "rn_resize_pair_u8_augment_workspace", "rn_resize_pair_u8_augment",
     "rn_resize_pair_u8_batch", "rn_resize_pair_u8_augment_batch_workspace", "rn_resize_pair_u8_augment_batch",
     "rn_dwgn_supported", "rn_dwgn_fwd", "rn_dwgn_bwd", "rn_depthwise_fwd", "rn_depthwise_dgrad", "rn_depthwise_wgrad_workspace", "rn_depthwise_wgrad", "rn_depthwise_bwd",
@@ -334,6 +347,7 @@ def lib():
                                                        C.c_void_p, C.c_int, C.c_void_p]
         L.rn_conv3x3_winograd_gn_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rn_conv3x3_winograd_gn_plan.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(WinoGnPlan)]
         L.rn_reduce_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.rn_conv2d_bias_grad.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p]

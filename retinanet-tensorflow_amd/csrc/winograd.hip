@@ -1505,7 +1505,81 @@ int check_fold(const rn_conv_seg* segs, int nseg, int cin, int cout, int tile) {
   }
   return RN_OK;
 }
+
+// do the blocks of a chunk kernel of width w stage the statistic rows of their sample in LDS (block_stats / block_coefs:
+// groups per block x chunks per sample <= STAGE_ROWS) in EVERY segment?
+bool rows_staged(const CArgs& a, int w, int cpg) {
+  const int ng = CK_LANES * w / cpg;
+  for (int s = 0; s < a.nseg; ++s)
+    if (ng * a.seg[s].cps > STAGE_ROWS) return false;
+  return true;
+}
 }  // namespace
+
+// What run_gn_fwd / run_gn_bwd decide for a layer, step by step as they decide it, without their launches (host only).
+extern "C" int rn_conv3x3_winograd_gn_plan(const rn_conv_seg* segs, int nseg, int cin, int cout, int tile, int in_groups, int out_groups,
+                                           rn_wino_gn_plan* plan) {
+  if (int e = check_fold(segs, nseg, cin, cout, tile)) return e;
+  RN_CHECK_ARG(plan && in_groups >= 0 && out_groups >= 0, "winograd gn plan: bad argument");
+  const bool fold_in = in_groups > 0, fold_out = out_groups > 0;
+  if (fold_in) RN_UNSUPPORTED(!fold_ok(cin, in_groups), "winograd gn plan: %d channels in %d groups cannot be folded", cin, in_groups);
+  if (fold_out) RN_UNSUPPORTED(!fold_ok(cout, out_groups), "winograd gn plan: %d channels in %d groups cannot be folded", cout, out_groups);
+  const int cpg_in = fold_in ? cin / in_groups : 0, cpg_out = fold_out ? cout / out_groups : 0;
+  // fill() wants the tensors of its segments: the plan reads none, any non-null address stands for them
+  static const float nowhere = 0.f;
+  rn_conv_seg tmp[RN_MAX_SEG];
+  for (int s = 0; s < nseg; ++s) {
+    tmp[s] = segs[s];
+    tmp[s].x = tmp[s].dy = &nowhere;
+    tmp[s].y = tmp[s].dx = const_cast<float*>(&nowhere);
+  }
+  *plan = rn_wino_gn_plan{};
+  CArgs xa = {}, ya = {};                               // the cin side (x, dx) and the cout side (y, dy) in chunks
+  cfill(segs, nseg, cin, tile, &xa, nullptr, nullptr, nullptr);
+  cfill(segs, nseg, cout, tile, &ya, nullptr, nullptr, nullptr);
+  plan->tiles = xa.total_tiles;
+  plan->chunks = xa.total_chunks;
+  for (int s = 0; s < nseg; ++s)
+    if ((xa.seg[s].th * xa.seg[s].tw) % CK_TILES != 0) plan->partial_chunk = 1;
+  plan->u_frag = rn::x3_bfrag_ok(xa.total_tiles, cin, cout) ? 1 : 0;
+  {  // run_gn_fwd
+    rn_wino_gn_plan_call& p = plan->fwd;
+    p.in_chunked = 1;
+    p.in_w = chunk_width(xa.total_tiles, cin, cpg_in);
+    p.in_slabs = cin / (CK_LANES * p.in_w);
+    p.in_staged = fold_in ? (rows_staged(xa, p.in_w, cpg_in) ? 1 : 0) : -1;
+    p.out_staged = -1;                                  // (the forward output side writes rows and reads none)
+    if (!fold_out) {
+      WArgs wia = {}, woa = {};
+      if (int e = fill(tmp, nseg, cin, cout, tile, false, &wia, &woa)) return e;
+      p.stride_w = width_for(woa.total_tiles, cout);
+    } else {
+      p.out_chunked = 1;
+      p.out_w = chunk_width(ya.total_tiles, cout, cpg_out);
+      p.out_slabs = cout / (CK_LANES * p.out_w);
+    }
+  }
+  {  // run_gn_bwd: dy (cout) is the input side, dx (cin) the output side
+    rn_wino_gn_plan_call& p = plan->bwd;
+    const int T_ = ya.total_tiles;
+    p.out_chunked = 1;
+    p.out_w = chunk_width(T_, cin, cpg_in);             // (wino_gn_bwd_post_kernel, and wino_gn_input_kernel where V is rebuilt)
+    p.out_slabs = cin / (CK_LANES * p.out_w);
+    p.out_staged = fold_in ? (rows_staged(xa, p.out_w, cpg_in) ? 1 : 0) : -1;
+    p.in_staged = -1;
+    if (fold_out) {
+      p.in_chunked = 1;
+      p.in_w = chunk_width(T_, cout, cpg_out);
+      p.in_slabs = cout / (CK_LANES * p.in_w);
+      p.in_staged = rows_staged(ya, p.in_w, cpg_out) ? 1 : 0;
+    } else {
+      WArgs wia = {}, woa = {};
+      if (int e = fill(tmp, nseg, cin, cout, tile, true, &wia, &woa, true)) return e;
+      p.stride_w = width_for(T_, cout);
+    }
+  }
+  return RN_OK;
+}
 
 // The kernel transforms of a folded layer ahead of the layer: U in the format its forward product reads (fp32 [P][cin][cout], or the
 // pre-split fragment image when rn_x3_bfrag_ok) -> u_out (rn_conv3x3_winograd_gn_u_bytes), the rotated kernel's transform (fp32, for

@@ -50,8 +50,9 @@ def _layerwise(xs, tower, ow, ob, act, groups):
 # (Wino<M>::g without contraction), and with base 17 ONE ReLU pre-activation of the ragged 128-channel case (index 1) came to lie
 # within rounding distance of zero -- it flips between the folded and the layer-by-layer evaluation and moves dx0 by 1.5e-2 of its
 # maximum (RN_TOWER_TEST_SEED=17 reproduces it; bases 18 ... 24 pass with either kernel-operand format).  A flip is a legitimate
-# difference between two correct fp32 evaluations (tests/test_gpu_fullsize.py arbitrates such cases with an fp64 oracle); the
-# case keeps its ReLU and its 1e-4 bar.
+# difference between two correct fp32 evaluations (tests/test_gpu_fullsize.py arbitrates such cases with an fp64 oracle, and
+# tests/test_gpu_wino_tower_cases.py compares the folded tower itself with fp64, its relu / relu6 seeds chosen clear of the kinks);
+# the case keeps its ReLU and its 1e-4 bar.
 SEED = int(os.environ.get("RN_TOWER_TEST_SEED", "18"))
 SHAPES = [  # (list of (n, h, w)), channels, out channels (0: no output conv), layers, act, tile
     ([(2, 16, 16), (2, 8, 8), (2, 4, 4), (2, 2, 2), (2, 1, 1)], 64, 36, 2, "elu", 4),     # pyramid incl. 1x1 map, box-like output
