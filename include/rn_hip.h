@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 417
+#define RN_API_VERSION 418
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -424,6 +424,48 @@ int rn_group_norm_fwd_f16_tiles(const rn_gn_seg* segs, int nseg, const rn_gn_par
 int rn_group_norm_bwd(const rn_gn_seg* segs, int nseg, const rn_gn_params* p, const float* gamma,
                       const float* beta, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                       rn_stream_t stream, rn_reduce_list* defer);
+/* Which kernels one rn_group_norm_fwd (backward == 0) or rn_group_norm_bwd (backward != 0) call with these segments, parameters
+ * and workspace size launches -- for tests that must know which implementation a shape takes.  It is the decision the two
+ * entry points themselves run before they launch (one function: the same constants, RN_GN_NO_SLICE / RN_GN_NO_ROWS /
+ * RN_GN_NO_COOP / RN_GN_SLICE_WC read at the call, RN_GN_ROWS_FIRST / RN_GN_SLICE_BIG / RN_GN_F16_STATS read once per process).
+ * Host only: touches no device, launches nothing.  Of the segments only n, hw, x_ld, dx_ld and dx_accumulate are read (data
+ * pointers may be NULL); of the parameters the pointers sync, stat_rows and stat_rows->rows are compared with NULL, never
+ * followed into device memory.  Returns what the launch would return for the same shapes: RN_EINVAL / RN_EUNSUPPORTED /
+ * RN_EWORKSPACE (workspace_bytes below rn_group_norm_workspace), RN_EINVAL for a NULL plan. */
+enum rn_gn_path {
+  RN_GN_PATH_PRODUCER_ROWS = 1, /* fwd: the producer's statistic rows (rn_gn_params.stat_rows) merged by gn_apply_rows_kernel   */
+  RN_GN_PATH_SLICE = 2,         /* gn_slice_{fwd,bwd}_kernel: one kernel, two-pass statistics in registers                      */
+  RN_GN_PATH_GRID_RESIDENT = 3, /* gn_coop_{fwd,bwd}_kernel: one kernel, blocks exchange tagged sums through rn_gn_params.sync  */
+  RN_GN_PATH_NARROW_SLICE = 4,  /* the slice kernels on runs narrower than 32 bytes, after the grid-resident path has declined  */
+  RN_GN_PATH_ROWS = 5,          /* gn_rows_partial_kernel + gn_[bwd_]apply_rows_kernel                                          */
+  RN_GN_PATH_THREE_KERNELS = 6  /* partial, finalize, apply                                                                     */
+};
+enum rn_gn_kernel { /* the three-kernel path's choices */
+  RN_GN_K_NONE = 0,
+  RN_GN_K_PARTIAL = 1, RN_GN_K_PARTIAL_F16X8 = 2,       /* statistics */
+  RN_GN_K_FINALIZE = 3, RN_GN_K_FINALIZE_COLS_SEGS = 4, /* finalize   */
+  RN_GN_K_APPLY = 5, RN_GN_K_APPLY_F16X8 = 6            /* apply      */
+};
+enum rn_gn_param_grad { /* backward: how dgamma / dbeta are formed */
+  RN_GN_PGRAD_NONE = 0,            /* forward */
+  RN_GN_PGRAD_FINALIZE_BLOCKS = 1, /* blocks appended to the gn_finalize_kernel launch sum the chunk partial planes     */
+  RN_GN_PGRAD_KERNEL = 2,          /* gn_param_grad_kernel sums the slice kernels' per-sample rows                      */
+  RN_GN_PGRAD_REDUCE_ROWS = 3      /* two rn_reduce_rows column sums (launched now, or recorded in the call's defer list) */
+};
+typedef struct rn_gn_plan {
+  int32_t path;                                 /* rn_gn_path */
+  int32_t slice_wc, slice_r, slice_blocks;      /* slice paths: channels per block, the kernels' template R, blocks; else 0 */
+  int32_t coop_r, coop_ppc, coop_blocks;        /* grid-resident path: float4 values per thread, pixels per block, blocks; else 0 */
+  int32_t rows_sw, rows_per_group;              /* rows paths: channel slab of the apply kernel; 1: rows hold per-group sums */
+  int32_t rows_apply_r, rows_apply_blocks;      /* rows paths: the apply kernel's template R and its pixel chunks (grid.x) */
+  int32_t rows_per_sample[RN_MAX_SEG];          /* rows paths: chunk rows per sample of every segment */
+  int32_t stats_kernel, finalize_kernel, apply_kernel;  /* three-kernel path: rn_gn_kernel; else RN_GN_K_NONE */
+  int32_t apply_blocks;                         /* three-kernel path: blocks per sample of the apply kernel */
+  int32_t param_grad, param_grad_deferred;      /* rn_gn_param_grad without / with a defer list given to rn_group_norm_bwd */
+  int32_t total_chunks;                         /* partial rows of the path taken (producer rows: the producer's) */
+} rn_gn_plan;
+int rn_group_norm_plan(const rn_gn_seg* segs, int nseg, const rn_gn_params* p, int backward, size_t workspace_bytes,
+                       rn_gn_plan* plan);
 
 /* ------------------------------------------------------------------ small elementwise ops
  * activation alone (retinanet.py:180-181 `activation` before the P7 conv) */

@@ -21,7 +21,7 @@ OPT_BLOCK = 1024
 LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
-API_VERSION = 417        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 418        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -127,6 +127,23 @@ class GnParams(C.Structure):
                 ("stat_rows", C.c_void_p)]
 
 
+class GnPlan(C.Structure):
+    """rn_gn_plan: the kernels one rn_group_norm_fwd / rn_group_norm_bwd call launches (rn_group_norm_plan, host only)"""
+    _fields_ = [("path", C.c_int32), ("slice_wc", C.c_int32), ("slice_r", C.c_int32), ("slice_blocks", C.c_int32),
+                ("coop_r", C.c_int32), ("coop_ppc", C.c_int32), ("coop_blocks", C.c_int32),
+                ("rows_sw", C.c_int32), ("rows_per_group", C.c_int32), ("rows_apply_r", C.c_int32), ("rows_apply_blocks", C.c_int32),
+                ("rows_per_sample", C.c_int32 * 16), ("stats_kernel", C.c_int32), ("finalize_kernel", C.c_int32),
+                ("apply_kernel", C.c_int32), ("apply_blocks", C.c_int32), ("param_grad", C.c_int32),
+                ("param_grad_deferred", C.c_int32), ("total_chunks", C.c_int32)]
+
+
+# enum rn_gn_path / rn_gn_kernel / rn_gn_param_grad
+GN_PATHS = {1: "producer_rows", 2: "slice", 3: "grid_resident", 4: "narrow_slice", 5: "rows", 6: "three_kernels"}
+GN_KERNELS = {0: None, 1: "gn_partial_kernel", 2: "gn_partial_f16x8_kernel", 3: "gn_finalize_kernel",
+              4: "gn_finalize_cols_segs_kernel", 5: "gn_apply_kernel", 6: "gn_apply_f16x8_kernel"}
+GN_PARAM_GRADS = {0: None, 1: "finalize_blocks", 2: "gn_param_grad_kernel", 3: "rn_reduce_rows"}
+
+
 class GnRows(C.Structure):
     """rn_gn_rows: partial (sum, sum of squares) rows a conv / depthwise forward wrote for the GroupNorm that follows"""
     _fields_ = [("rows", C.c_void_p), ("rows_per_sample", C.c_int32), ("per_group", C.c_int32), ("groups", C.c_int32)]
@@ -220,7 +237,7 @@ SYMBOLS = [
     "rn_resize_pair_u8_augment_workspace", "rn_resize_pair_u8_augment",
     "rn_resize_pair_u8_batch", "rn_resize_pair_u8_augment_batch_workspace", "rn_resize_pair_u8_augment_batch",
     "rn_dwgn_supported", "rn_dwgn_fwd", "rn_dwgn_bwd", "rn_depthwise_fwd", "rn_depthwise_dgrad", "rn_depthwise_wgrad_workspace", "rn_depthwise_wgrad", "rn_depthwise_bwd",
-    "rn_group_norm_sync_bytes", "rn_group_norm_workspace", "rn_group_norm_fwd", "rn_group_norm_bwd",
+    "rn_group_norm_sync_bytes", "rn_group_norm_workspace", "rn_group_norm_fwd", "rn_group_norm_bwd", "rn_group_norm_plan",
     "rn_act_fwd", "rn_act_bwd", "rn_upsample_add_fwd", "rn_upsample_add_bwd_top",
     "rn_pack_weights_f16", "rn_pack_weights_f16_bytes", "rn_cast_f32_to_f16", "rn_pad_cast_rgb_f16", "rn_conv2d_fwd_f16", "rn_conv2d_f16_fold_rows", "rn_conv2d_fwd_f16_fold", "rn_group_norm_finalize", "rn_group_norm_apply_f16", "rn_group_norm_apply_res_f16", "rn_maxpool_fwd_f16", "rn_maxpool_gn_fwd_f16", "rn_upsample_add_fwd_f16",
     "rn_act_fwd_f16", "rn_flip_width", "rn_dropout", "rn_dropout_strided", "rn_maxpool_fwd", "rn_maxpool_bwd", "rn_maxpool_bwd_arg", "rn_avgpool_fwd", "rn_avgpool_bwd",
@@ -348,6 +365,7 @@ def lib():
         L.rn_conv3x3_winograd_gn_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_conv3x3_winograd_gn_plan.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(WinoGnPlan)]
+        L.rn_group_norm_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.POINTER(GnPlan)]
         L.rn_reduce_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.rn_conv2d_bias_grad.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p]

@@ -5,7 +5,14 @@
 // HBM-bound.  Forward = 1 read for the statistics + 1 read / 1 write for the apply pass;
 // backward = 2 reads of (x, dy) + 1 write.  Statistics are reduced in a fixed order
 // (per-thread fp32 over a short run -> LDS tree -> per-chunk partial -> fp64 finalize), so the
-// result is bitwise reproducible and safe against E[x^2]-E[x]^2 cancellation.
+// result is bitwise reproducible.  E[x^2]-E[x]^2 cancellation: the slice-resident kernels take
+// two-pass statistics (mean, then the squared deviations) and have none.  Every other path sums
+// x and x^2 in fp32 per chunk and only merges the chunks in fp64, so the rounding of the chunk
+// sums enters the variance as a difference of two nearly equal numbers once |mean| >> std.
+// Measured against fp64 at the two values tests/test_gpu_gn_cases.py holds (profiles/
+// gn_cases_err.txt): at mean/std = 0.25 every tensor is within 3e-7 of fp64; at mean/std = 16
+// rstd is off by 1e-6 to 3.6e-5 depending on the shape (3 to 300 times the fp32 reference's own
+// error) -- inside the 1e-4 bar.  Nothing was measured beyond 16.
 // Several tensors that share gamma/beta (one head layer over P3..P7) are one launch.
 #include "rn_common.h"
 
@@ -1320,12 +1327,13 @@ bool plan_coop(GnArgs* a) {
   const int lanes = CT / CQ;
   // smallest per-thread depth (most blocks, most parallelism) that keeps the grid within COOP_MAX_BLOCKS
   int r = 0, ppc = 0, chunks = 0;
-  for (int cand = 4; cand <= COOP_MAX_R; cand *= 2) {
+  // (no depth 8: ceil(hw / 4L) <= 2 ceil(hw / 8L), so a grid above 256 blocks at depth 4 is above 128 at depth 8)
+  for (int cand = 4; cand <= COOP_MAX_R; cand *= 4) {
     ppc = lanes * cand;
     chunks = 0;
     for (int s = 0; s < a->nseg; ++s) chunks += a->seg[s].n * rn::ceil_div(a->seg[s].hw, ppc);
     // depth 4 needs ~80 VGPRs: three blocks fit a CU, so two concurrent kernels of 256 blocks are still co-resident;
-    // deeper variants (up to 245 VGPRs, one block per CU) stay within 128 blocks each
+    // depth 16 (up to 245 VGPRs, one block per CU) stays within 128 blocks
     if (chunks <= (cand == 4 ? 2 * COOP_MAX_BLOCKS : COOP_MAX_BLOCKS)) { r = cand; break; }
   }
   if (!r) return false;
@@ -1354,7 +1362,6 @@ void launch_coop(const GnArgs& a, hipStream_t st) {
 #define RN_GN_COOP(ACT_)                                                                                       \
   do {                                                                                                          \
     if (a.coop_r == 4) RN_GN_COOP2(ACT_, 4);                                                                    \
-    else if (a.coop_r == 8) RN_GN_COOP2(ACT_, 8);                                                               \
     else RN_GN_COOP2(ACT_, 16);                                                                                 \
   } while (0)
   switch (a.act) {
@@ -1415,16 +1422,20 @@ bool narrow_slice_ok(const GnArgs& a) {
   return elems * (8 / a.slice_wc) <= (1L << 21);
 }
 
+unsigned slice_blocks(const GnArgs& a) { return (unsigned)(a.total_samples * (a.groups / (a.slice_wc / a.cpg))); }
+// template R of the slice kernels for plan_slices' r
+int slice_template_r(int r) { return r <= 2 ? 2 : r >= 32 ? 32 : r; }
+
 template <bool BWD, int ACT>
 void launch_slices_act(const GnArgs& a, int r, hipStream_t st) {
-  const unsigned blocks = (unsigned)(a.total_samples * (a.groups / (a.slice_wc / a.cpg)));
+  const unsigned blocks = slice_blocks(a);
 #define RN_GN_SLICE(R_)                                                                                  \
   do {                                                                                                   \
     if (BWD) hipLaunchKernelGGL((gn_slice_bwd_kernel<R_, ACT>), dim3(blocks), dim3(ST), 0, st, a);       \
     else hipLaunchKernelGGL((gn_slice_fwd_kernel<R_, ACT>), dim3(blocks), dim3(ST), 0, st, a);           \
   } while (0)
-  switch (r) {
-    case 1: case 2: RN_GN_SLICE(2); break;
+  switch (slice_template_r(r)) {
+    case 2: RN_GN_SLICE(2); break;
     case 4: RN_GN_SLICE(4); break;
     case 8: RN_GN_SLICE(8); break;
     case 16: RN_GN_SLICE(16); break;
@@ -1442,7 +1453,8 @@ void launch_slices(const GnArgs& a, int r, hipStream_t st) {
   }
 }
 
-int build_args(const rn_gn_seg* segs, int nseg, const rn_gn_params* p, GnArgs* a, bool bwd) {
+// query: the host-only plan query -- the segments' data pointers are neither checked nor used
+int build_args(const rn_gn_seg* segs, int nseg, const rn_gn_params* p, GnArgs* a, bool bwd, bool query = false) {
   RN_CHECK_ARG(segs && p, "group_norm: null argument");
   RN_CHECK_ARG(nseg >= 1 && nseg <= RN_MAX_SEG, "group_norm: nseg %d outside [1,%d]", nseg, RN_MAX_SEG);
   RN_CHECK_ARG(p->c >= 4 && p->groups >= 1 && p->c % p->groups == 0, "group_norm: c=%d groups=%d", p->c, p->groups);
@@ -1457,10 +1469,15 @@ int build_args(const rn_gn_seg* segs, int nseg, const rn_gn_params* p, GnArgs* a
   a->sync = (unsigned*)p->sync;
   int samples = 0, chunks = 0;
   for (int s = 0; s < nseg; ++s) {
-    RN_CHECK_ARG(segs[s].x && segs[s].mean && segs[s].rstd && segs[s].n >= 1 && segs[s].hw >= 1,
+    RN_CHECK_ARG((query || (segs[s].x && segs[s].mean && segs[s].rstd)) && segs[s].n >= 1 && segs[s].hw >= 1,
                  "group_norm: bad segment %d", s);
-    if (bwd) RN_CHECK_ARG(segs[s].dy && segs[s].dx, "group_norm bwd: null dy/dx in segment %d", s);
-    else RN_CHECK_ARG(segs[s].y, "group_norm fwd: null y in segment %d", s);
+    if (!query) {
+      if (bwd) {
+        RN_CHECK_ARG(segs[s].dy && segs[s].dx, "group_norm bwd: null dy/dx in segment %d", s);
+      } else {
+        RN_CHECK_ARG(segs[s].y, "group_norm fwd: null y in segment %d", s);
+      }
+    }
     GnSeg& d = a->seg[s];
     d.x = segs[s].x; d.y = segs[s].y; d.res = segs[s].residual; d.dy = segs[s].dy; d.dx = segs[s].dx;
     d.dres = segs[s].dresidual;
@@ -1529,6 +1546,7 @@ extern "C" size_t rn_group_norm_workspace(const rn_gn_seg* segs, int nseg, const
   if (!segs || !p || nseg < 1 || nseg > RN_MAX_SEG || p->c < 4 || p->groups < 1) return 0;
   int samples = 0, chunks = 0;
   for (int s = 0; s < nseg; ++s) {
+    if (segs[s].n < 1 || segs[s].hw < 1) return 0;   // (the launches refuse such a segment; hw = 0 would divide by zero below)
     long elems = (long)segs[s].hw * p->c;
     const long per = elems >= (4L << 20) ? 16384 : 4096;
     int ck = (int)((elems + per - 1) / per);
@@ -1574,8 +1592,8 @@ bool rows_path_ok(const GnArgs& a) {
     if (!rn_group_norm_rows_ok(a.c, a.groups, a.seg[s].chunks, 1)) return false;
   return true;
 }
-template <bool BWD>
-void launch_apply_rows(const GnArgs& a, hipStream_t st) {
+// the apply kernel of the rows paths (a.rows_sw, a.rows_per_group and every segment's chunks are set): template R and pixel chunks
+void plan_apply_rows(const GnArgs& a, bool bwd, rn_gn_plan* plan) {
   int max_hw = 0, max_chunks = 0;
   for (int s = 0; s < a.nseg; ++s) {
     max_hw = max_hw > a.seg[s].hw ? max_hw : a.seg[s].hw;
@@ -1586,8 +1604,15 @@ void launch_apply_rows(const GnArgs& a, hipStream_t st) {
   const long entries = (long)max_chunks * (a.rows_per_group ? a.rows_sw / a.cpg : a.rows_sw);
   const int chunk_cap = entries <= 2048 ? 4096 : 48;
   int R = 4;
-  while (R < (BWD ? 8 : 16) && rn::ceil_div(max_hw, lanes * R) > chunk_cap) R *= 2;   // (backward holds x, dy and the residual)
-  const dim3 grid((unsigned)rn::ceil_div(max_hw, lanes * R), (unsigned)(a.c / a.rows_sw), (unsigned)a.total_samples);
+  while (R < (bwd ? 8 : 16) && rn::ceil_div(max_hw, lanes * R) > chunk_cap) R *= 2;   // (backward holds x, dy and the residual)
+  plan->rows_sw = a.rows_sw; plan->rows_per_group = a.rows_per_group;
+  plan->rows_apply_r = R; plan->rows_apply_blocks = rn::ceil_div(max_hw, lanes * R);
+  for (int s = 0; s < a.nseg; ++s) plan->rows_per_sample[s] = a.seg[s].chunks;
+}
+template <bool BWD>
+void launch_apply_rows(const GnArgs& a, const rn_gn_plan& plan, hipStream_t st) {
+  const int R = plan.rows_apply_r;
+  const dim3 grid((unsigned)plan.rows_apply_blocks, (unsigned)(a.c / a.rows_sw), (unsigned)a.total_samples);
 #define RN_GN_ROWS2(ACT_, R_)                                                                                \
   do {                                                                                                       \
     if (BWD) hipLaunchKernelGGL((gn_bwd_apply_rows_kernel<ACT_, R_>), grid, dim3(AT), 0, st, a);             \
@@ -1624,7 +1649,87 @@ bool rows_first() {
   static const bool v = getenv("RN_GN_ROWS_FIRST") && atoi(getenv("RN_GN_ROWS_FIRST")) != 0;
   return v;
 }
+// RN_GN_F16_STATS=0: the generic statistics / finalize kernels on the three-kernel path (A/B)
+bool f16_stats() {
+  static const bool v = !(getenv("RN_GN_F16_STATS") && atoi(getenv("RN_GN_F16_STATS")) == 0);
+  return v;
+}
+
+// THE dispatch of rn_group_norm_fwd / rn_group_norm_bwd: which implementation this call takes and with which template
+// parameters and grids.  Fills *plan and the chunking / slab fields of *a that the chosen path's kernels read (no pointers:
+// the entry points add those); rn_group_norm_plan returns the same plan without launching.
+// Order: the producer's rows (fwd); the slice-resident kernel when its blocks read runs of >= 32 bytes; the rows path where
+// RN_GN_ROWS_FIRST asks for it; the grid-resident kernel (full rows); the narrow slice kernel; the rows path; three kernels.
+void decide(GnArgs* a, const rn_gn_params* p, bool bwd, size_t workspace_bytes, rn_gn_plan* plan) {
+  *plan = rn_gn_plan{};
+  plan->total_chunks = a->total_chunks;
+  if (!bwd && p->stat_rows && p->stat_rows->rows && a->nseg == 1 && !a->in_half && !a->out_half && !a->strided && a->act != RN_ACT_SIGMOID &&
+      p->stat_rows->groups == a->groups && rn_group_norm_rows_ok(a->c, a->groups, p->stat_rows->rows_per_sample, p->stat_rows->per_group)) {
+    // x came with partial-sum rows from its producer: merge them and apply in one pass
+    a->rows_per_group = p->stat_rows->per_group;
+    a->seg[0].chunks = p->stat_rows->rows_per_sample; a->seg[0].chunk_start = 0;
+    a->rows_sw = rows_slab(a->c, a->cpg);
+    plan->path = RN_GN_PATH_PRODUCER_ROWS;
+    plan->total_chunks = a->seg[0].n * a->seg[0].chunks;
+    plan_apply_rows(*a, false, plan);
+    return;
+  }
+  const int r = plan_slices(a);
+  auto slices = [&](int path) {
+    plan->path = path;
+    plan->slice_wc = a->slice_wc; plan->slice_r = slice_template_r(r); plan->slice_blocks = (int)slice_blocks(*a);
+    // per-sample (sum g, sum g xhat) rows: gn_param_grad_kernel, or two rows of the step's single deferred reduction launch
+    if (bwd) { plan->param_grad = RN_GN_PGRAD_KERNEL; plan->param_grad_deferred = RN_GN_PGRAD_REDUCE_ROWS; }
+  };
+  auto rows_path = [&]() {   // statistics rows per chunk, then merge + apply: two kernels, nothing waits on another block
+    a->rows_per_group = 1; a->rows_sw = rows_slab(a->c, a->cpg);
+    plan->path = RN_GN_PATH_ROWS;
+    plan_apply_rows(*a, bwd, plan);
+    if (bwd) plan->param_grad = plan->param_grad_deferred = RN_GN_PGRAD_REDUCE_ROWS;   // column sums of the two partial planes
+  };
+  if (r && slice_preferred(*a)) return slices(RN_GN_PATH_SLICE);
+  const bool rows_ok = rows_path_ok(*a);
+  if (rows_ok && rows_first()) return rows_path();
+  {
+    GnArgs c = *a;  // the chunking differs from the three-kernel path's; the workspace (chunks <= 256 rows) always fits
+    if (plan_coop(&c) && ws_bytes(c) <= workspace_bytes) {
+      *a = c;
+      plan->path = RN_GN_PATH_GRID_RESIDENT;
+      plan->coop_r = a->coop_r; plan->coop_ppc = a->coop_ppc; plan->coop_blocks = a->total_chunks;
+      plan->total_chunks = a->total_chunks;
+      if (bwd) plan->param_grad = plan->param_grad_deferred = RN_GN_PGRAD_REDUCE_ROWS;
+      return;
+    }
+  }
+  if (r && narrow_slice_ok(*a)) return slices(RN_GN_PATH_NARROW_SLICE);
+  if (rows_ok) return rows_path();
+  plan->path = RN_GN_PATH_THREE_KERNELS;
+  const int c8 = a->c >> 3;
+  plan->stats_kernel = (!bwd && f16_stats() && a->in_half && !a->strided && a->c % 8 == 0 && c8 <= T && T % c8 == 0) ? RN_GN_K_PARTIAL_F16X8
+                                                                                                                 : RN_GN_K_PARTIAL;
+  plan->finalize_kernel = (!bwd && f16_stats() && a->c % 64 == 0 && a->cpg <= 64 && 64 % a->cpg == 0) ? RN_GN_K_FINALIZE_COLS_SEGS
+                                                                                                    : RN_GN_K_FINALIZE;
+  const bool half_apply = !bwd && a->in_half && a->out_half && a->c % 8 == 0 && a->drop_rate == 0.f;
+  plan->apply_kernel = half_apply ? RN_GN_K_APPLY_F16X8 : RN_GN_K_APPLY;
+  plan->apply_blocks = (int)apply_blocks(*a, half_apply ? 8 : 4);
+  // dbeta / dgamma = the column sums of the two partial planes: blocks appended to the finalize launch, or -- while
+  // the step's reductions are deferred -- two rows of the single batched reduction
+  if (bwd) { plan->param_grad = RN_GN_PGRAD_FINALIZE_BLOCKS; plan->param_grad_deferred = RN_GN_PGRAD_REDUCE_ROWS; }
+}
 }  // namespace
+
+extern "C" int rn_group_norm_plan(const rn_gn_seg* segs, int nseg, const rn_gn_params* p, int backward, size_t workspace_bytes,
+                                  rn_gn_plan* plan) {
+  RN_CHECK_ARG(plan, "group_norm plan: null plan");
+  GnArgs a = {};
+  if (int e = build_args(segs, nseg, p, &a, backward != 0, true)) return e;
+  if (workspace_bytes < ws_bytes(a)) {
+    rn::set_error("group_norm plan: workspace %zu < %zu", workspace_bytes, ws_bytes(a));
+    return RN_EWORKSPACE;
+  }
+  decide(&a, p, backward != 0, workspace_bytes, plan);
+  return RN_OK;
+}
 
 extern "C" int rn_group_norm_fwd(const rn_gn_seg* segs, int nseg, const rn_gn_params* p, const float* gamma,
                                  const float* beta, void* workspace, size_t workspace_bytes, rn_stream_t stream) {
@@ -1637,76 +1742,48 @@ extern "C" int rn_group_norm_fwd(const rn_gn_seg* segs, int nseg, const rn_gn_pa
   }
   a.gamma = gamma; a.beta = beta; a.partial = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  if (p->stat_rows && p->stat_rows->rows && a.nseg == 1 && !a.in_half && !a.out_half && !a.strided && a.act != RN_ACT_SIGMOID &&
-      p->stat_rows->groups == a.groups && rn_group_norm_rows_ok(a.c, a.groups, p->stat_rows->rows_per_sample, p->stat_rows->per_group)) {
-    // x came with partial-sum rows from its producer: merge them and apply in one pass
-    a.rows = (const float2*)p->stat_rows->rows; a.rows_per_group = p->stat_rows->per_group;
-    a.seg[0].chunks = p->stat_rows->rows_per_sample; a.seg[0].chunk_start = 0;
-    a.rows_sw = rows_slab(a.c, a.cpg);
-    launch_apply_rows<false>(a, st);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-  }
-  // slice-resident kernel when its blocks read runs of >= 32 bytes; else the grid-resident kernel (full rows); else
-  // the narrow slice kernel; else three kernels
-  const int r = plan_slices(&a);
-  if (r && slice_preferred(a)) {
-    launch_slices<false>(a, r, st);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-  }
-  const bool rows_ok = rows_path_ok(a);
-  auto rows_path = [&]() {   // statistics rows per chunk, then merge + apply: two kernels, nothing waits on another block
-    a.rows_out = rows_area(a, workspace); a.rows = a.rows_out; a.rows_per_group = 1; a.rows_sw = rows_slab(a.c, a.cpg);
-    launch_rows_partial<false>(a, st);
-    launch_apply_rows<false>(a, st);
-  };
-  if (rows_ok && rows_first()) {
-    rows_path();
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-  }
-  {
-    GnArgs c = a;  // the chunking differs from the three-kernel path's; the workspace (chunks <= 128 rows) always fits
-    if (plan_coop(&c) && ws_bytes(c) <= workspace_bytes) {
-      c.xchg = (unsigned long long*)((char*)c.sync + COOP_XCHG_OFFSET);
-      launch_coop<false>(c, st);
-      RN_LAUNCH_CHECK();
-      return RN_OK;
+  rn_gn_plan plan;
+  decide(&a, p, false, workspace_bytes, &plan);
+  switch (plan.path) {
+    case RN_GN_PATH_PRODUCER_ROWS:
+      a.rows = (const float2*)p->stat_rows->rows;
+      launch_apply_rows<false>(a, plan, st);
+      break;
+    case RN_GN_PATH_SLICE:
+    case RN_GN_PATH_NARROW_SLICE:
+      launch_slices<false>(a, plan.slice_r, st);
+      break;
+    case RN_GN_PATH_GRID_RESIDENT:
+      a.xchg = (unsigned long long*)((char*)a.sync + COOP_XCHG_OFFSET);
+      launch_coop<false>(a, st);
+      break;
+    case RN_GN_PATH_ROWS:
+      a.rows_out = rows_area(a, workspace); a.rows = a.rows_out;
+      launch_rows_partial<false>(a, st);
+      launch_apply_rows<false>(a, plan, st);
+      break;
+    default: {
+      if (plan.stats_kernel == RN_GN_K_PARTIAL_F16X8)
+        hipLaunchKernelGGL(gn_partial_f16x8_kernel, dim3(a.total_chunks), dim3(T), 0, st, a);
+      else
+        hipLaunchKernelGGL(gn_partial_kernel<false>, dim3(a.total_chunks), dim3(T), 0, st, a);
+      if (plan.finalize_kernel == RN_GN_K_FINALIZE_COLS_SEGS)
+        hipLaunchKernelGGL(gn_finalize_cols_segs_kernel, dim3(a.total_samples * (a.c / 64)), dim3(T), 0, st, a);
+      else
+        hipLaunchKernelGGL(gn_finalize_kernel<false>, dim3(a.total_samples * a.groups), dim3(T), 0, st, a);
+      const dim3 grid((unsigned)plan.apply_blocks, (unsigned)a.total_samples);
+      if (plan.apply_kernel == RN_GN_K_APPLY_F16X8)
+        switch (a.act) {  // activation as a template parameter: no per-element switch in a bandwidth-bound pass
+          case RN_ACT_RELU: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_RELU>, grid, dim3(T), 0, st, a); break;
+          case RN_ACT_ELU: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_ELU>, grid, dim3(T), 0, st, a); break;
+          case RN_ACT_RELU6: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_RELU6>, grid, dim3(T), 0, st, a); break;
+          case RN_ACT_SIGMOID: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_SIGMOID>, grid, dim3(T), 0, st, a); break;
+          default: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_NONE>, grid, dim3(T), 0, st, a); break;
+        }
+      else
+        hipLaunchKernelGGL(gn_apply_kernel<false>, grid, dim3(T), 0, st, a);
     }
   }
-  if (r && narrow_slice_ok(a)) {
-    launch_slices<false>(a, r, st);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-  }
-  if (rows_ok) {
-    rows_path();
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-  }
-  {
-    static const bool f16_stats = !(getenv("RN_GN_F16_STATS") && atoi(getenv("RN_GN_F16_STATS")) == 0);     // (0: the generic kernels; A/B)
-    const int c8 = a.c >> 3;
-    if (f16_stats && a.in_half && !a.strided && a.c % 8 == 0 && c8 <= T && T % c8 == 0)
-      hipLaunchKernelGGL(gn_partial_f16x8_kernel, dim3(a.total_chunks), dim3(T), 0, st, a);
-    else
-      hipLaunchKernelGGL(gn_partial_kernel<false>, dim3(a.total_chunks), dim3(T), 0, st, a);
-    if (f16_stats && a.c % 64 == 0 && a.cpg <= 64 && 64 % a.cpg == 0)
-      hipLaunchKernelGGL(gn_finalize_cols_segs_kernel, dim3(a.total_samples * (a.c / 64)), dim3(T), 0, st, a);
-    else
-      hipLaunchKernelGGL(gn_finalize_kernel<false>, dim3(a.total_samples * a.groups), dim3(T), 0, st, a);
-  }
-  if (a.in_half && a.out_half && a.c % 8 == 0 && a.drop_rate == 0.f)
-    switch (a.act) {  // activation as a template parameter: no per-element switch in a bandwidth-bound pass
-      case RN_ACT_RELU: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_RELU>, dim3(apply_blocks(a, 8), a.total_samples), dim3(T), 0, st, a); break;
-      case RN_ACT_ELU: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_ELU>, dim3(apply_blocks(a, 8), a.total_samples), dim3(T), 0, st, a); break;
-      case RN_ACT_RELU6: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_RELU6>, dim3(apply_blocks(a, 8), a.total_samples), dim3(T), 0, st, a); break;
-      case RN_ACT_SIGMOID: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_SIGMOID>, dim3(apply_blocks(a, 8), a.total_samples), dim3(T), 0, st, a); break;
-      default: hipLaunchKernelGGL(gn_apply_f16x8_kernel<RN_ACT_NONE>, dim3(apply_blocks(a, 8), a.total_samples), dim3(T), 0, st, a); break;
-    }
-  else
-    hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(apply_blocks(a), a.total_samples), dim3(T), 0, st, a);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }
@@ -1762,60 +1839,41 @@ extern "C" int rn_group_norm_bwd(const rn_gn_seg* segs, int nseg, const rn_gn_pa
   a.partial = (float*)workspace;
   a.coef = (float*)((char*)workspace + rn::align_up((size_t)a.total_chunks * a.c * 2 * sizeof(float), 256));
   hipStream_t st = (hipStream_t)stream;
-  int r = plan_slices(&a);
-  const bool rows_ok = rows_path_ok(a);
-  auto rows_path = [&]() -> int {   // (sum g, sum g xhat) rows per chunk, then merge + apply; parameter gradients = column sums
-    a.rows_out = rows_area(a, workspace); a.rows = a.rows_out; a.rows_per_group = 1; a.rows_sw = rows_slab(a.c, a.cpg);
-    launch_rows_partial<true>(a, st);
-    launch_apply_rows<true>(a, st);
-    RN_LAUNCH_CHECK();
-    if (int e = rn::launch_reduce_rows(a.partial, dbeta, a.c, a.total_chunks, 0, st)) return e;
-    return rn::launch_reduce_rows(a.partial + (size_t)a.total_chunks * a.c, dgamma, a.c, a.total_chunks, 0, st);
-  };
-  if (rows_ok && rows_first() && !(r && slice_preferred(a))) return rows_path();
-  bool coop_first = r && !slice_preferred(a);
-  if (coop_first) {
-    GnArgs c = a;
-    coop_first = plan_coop(&c) && ws_bytes(c) <= workspace_bytes;
-    if (!coop_first && !narrow_slice_ok(a)) r = 0;  // neither: three kernels
-  }
-  if (r && !coop_first) {
-    a.pgrad = (float*)workspace;  // [2][total_samples][c] <= the chunk-partial area (chunks >= samples)
-    launch_slices<true>(a, r, st);
-    if (rn::reduce_deferred(st)) {  // the two row sums join the step's single deferred reduction launch
-      RN_LAUNCH_CHECK();
-      if (int e = rn::launch_reduce_rows(a.pgrad, dbeta, a.c, a.total_samples, 0, st)) return e;
-      return rn::launch_reduce_rows(a.pgrad + (size_t)a.total_samples * a.c, dgamma, a.c, a.total_samples, 0, st);
-    }
-    hipLaunchKernelGGL(gn_param_grad_kernel, dim3(rn::ceil_div(a.c, 256)), dim3(256), 0, st, a);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-  }
-  {
-    GnArgs c = a;
-    if (plan_coop(&c) && ws_bytes(c) <= workspace_bytes) {
-      c.xchg = (unsigned long long*)((char*)c.sync + COOP_XCHG_OFFSET);
-      launch_coop<true>(c, st);
-      RN_LAUNCH_CHECK();
-      // dbeta / dgamma = column sums of the two partial planes (one deferred launch per step, or two small ones now)
-      if (int e = rn::launch_reduce_rows(c.partial, dbeta, c.c, c.total_chunks, 0, st)) return e;
-      return rn::launch_reduce_rows(c.partial + (size_t)c.total_chunks * c.c, dgamma, c.c, c.total_chunks, 0, st);
-    }
-  }
-  if (rows_ok) return rows_path();
-  hipLaunchKernelGGL(gn_partial_kernel<true>, dim3(a.total_chunks), dim3(T), 0, st, a);
-  // dbeta / dgamma = the column sums of the two partial planes: blocks appended to the finalize launch, or -- while
-  // the step's reductions are deferred -- two rows of the single batched reduction
+  rn_gn_plan plan;
+  decide(&a, p, true, workspace_bytes, &plan);
   const bool deferring = rn::reduce_deferred(st);
-  hipLaunchKernelGGL(gn_finalize_kernel<true>, dim3(a.total_samples * a.groups + (deferring ? 0 : rn::ceil_div(a.c, 16))), dim3(T), 0,
-                     st, a);
-  hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(apply_blocks(a), a.total_samples), dim3(T), 0, st, a);
-  RN_LAUNCH_CHECK();
-  if (deferring) {
-    if (int e = rn::launch_reduce_rows(a.partial, dbeta, a.c, a.total_chunks, 0, st)) return e;
-    return rn::launch_reduce_rows(a.partial + (size_t)a.total_chunks * a.c, dgamma, a.c, a.total_chunks, 0, st);
+  const int param_grad = deferring ? plan.param_grad_deferred : plan.param_grad;
+  const float* rows = a.partial;   // [2][nrows][c]: plane 0 sums to dbeta, plane 1 to dgamma
+  int nrows = a.total_chunks;
+  switch (plan.path) {
+    case RN_GN_PATH_SLICE:
+    case RN_GN_PATH_NARROW_SLICE:
+      a.pgrad = (float*)workspace;  // [2][total_samples][c] <= the chunk-partial area (chunks >= samples)
+      launch_slices<true>(a, plan.slice_r, st);
+      if (param_grad == RN_GN_PGRAD_KERNEL) hipLaunchKernelGGL(gn_param_grad_kernel, dim3(rn::ceil_div(a.c, 256)), dim3(256), 0, st, a);
+      rows = a.pgrad; nrows = a.total_samples;
+      break;
+    case RN_GN_PATH_GRID_RESIDENT:
+      a.xchg = (unsigned long long*)((char*)a.sync + COOP_XCHG_OFFSET);
+      launch_coop<true>(a, st);
+      break;
+    case RN_GN_PATH_ROWS:   // (sum g, sum g xhat) rows per chunk, then merge + apply
+      a.rows_out = rows_area(a, workspace); a.rows = a.rows_out;
+      launch_rows_partial<true>(a, st);
+      launch_apply_rows<true>(a, plan, st);
+      break;
+    default:
+      hipLaunchKernelGGL(gn_partial_kernel<true>, dim3(a.total_chunks), dim3(T), 0, st, a);
+      hipLaunchKernelGGL(gn_finalize_kernel<true>,
+                         dim3(a.total_samples * a.groups + (param_grad == RN_GN_PGRAD_FINALIZE_BLOCKS ? rn::ceil_div(a.c, 16) : 0)), dim3(T), 0,
+                         st, a);
+      hipLaunchKernelGGL(gn_apply_kernel<true>, dim3((unsigned)plan.apply_blocks, a.total_samples), dim3(T), 0, st, a);
   }
-  return RN_OK;
+  RN_LAUNCH_CHECK();
+  if (param_grad != RN_GN_PGRAD_REDUCE_ROWS) return RN_OK;
+  // dbeta / dgamma = column sums of the two planes (one deferred launch per step, or two small ones now)
+  if (int e = rn::launch_reduce_rows(rows, dbeta, a.c, nrows, 0, st)) return e;
+  return rn::launch_reduce_rows(rows + (size_t)nrows * a.c, dgamma, a.c, nrows, 0, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

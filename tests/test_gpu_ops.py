@@ -181,17 +181,48 @@ def test_group_norm_act_fwd_bwd(dev, c, act, res):
     assert_close(bg.grad.cpu().numpy(), bc.grad.numpy(), TOL, "gn dbeta")
 
 
+# the implementation a mode of the two tests below names, as rn_group_norm_plan reports it ("default": the slice kernels)
+_GN_MODE_PATHS = {"default": ("slice", "narrow_slice"), "rows": ("rows",), "grid_resident": ("grid_resident",),
+                  "three_kernel": ("three_kernels",)}
+
+
+def _gn_paths(dev, shapes, c, act, drop_rate=0.0):
+    """The (forward, backward) implementations ops.group_norm_act's calls take on these shapes under the current switches:
+    the host-only plan query on the parameters ops builds (sync region included) and the workspace size it asks for."""
+    import ctypes as C
+    import _rn
+    import ops
+    L = _rn.lib()
+    params = ops._gn_params(c, ops.gn_groups(c, 32), 1e-5, act, drop_rate, 1234, None, False, dev)
+    segs = (_rn.GnSeg * len(shapes))()
+    for s, shp in zip(segs, shapes):
+        s.n, s.hw = shp[0], shp[1] * shp[2]
+    need = L.rn_group_norm_workspace(segs, len(shapes), C.byref(params))
+    names = []
+    for backward in (0, 1):
+        plan = _rn.GnPlan()
+        _rn.check(L.rn_group_norm_plan(segs, len(shapes), C.byref(params), backward, need, C.byref(plan)), "rn_group_norm_plan")
+        names.append(_rn.GN_PATHS[plan.path])
+    return names
+
+
 @pytest.mark.parametrize("mode", ["default", "grid_resident", "three_kernel"])
 def test_group_norm_dropout_is_consistent(dev, monkeypatch, mode):
     """Dropout mask: right keep fraction, inverted scaling, and backward uses the SAME mask -- and the SAME mask in all
     three GroupNorm implementations (the mask is a function of the element index only)."""
+    import _rn
     import ops
     if mode != "default":
         monkeypatch.setenv("RN_GN_NO_SLICE", "1")
+    if mode == "grid_resident":
+        monkeypatch.setattr(ops, "GN_GRID_RESIDENT", True)     # (off by default: without the sync region that path declines)
     if mode == "three_kernel":
         monkeypatch.setenv("RN_GN_NO_COOP", "1")
+        monkeypatch.setenv("RN_GN_NO_ROWS", "1")               # (the rows path would take this shape in front of the three kernels)
     torch.manual_seed(0)
     c = 64
+    for path in _gn_paths(dev, [(2, 32, 32, c)], c, None, 0.25):
+        assert path in _GN_MODE_PATHS[mode], "mode %s runs the %s implementation" % (mode, path)
     x = torch.randn(2, 32, 32, c, device=dev, requires_grad=True)
     gamma = torch.ones(c, device=dev, requires_grad=True)
     beta = torch.zeros(c, device=dev, requires_grad=True)
@@ -209,6 +240,7 @@ def test_group_norm_dropout_is_consistent(dev, monkeypatch, mode):
     assert torch.allclose(beta.grad, expect, rtol=1e-4)
     _DROPOUT_MASKS.append(kept.cpu())
     assert torch.equal(_DROPOUT_MASKS[0], _DROPOUT_MASKS[-1])       # same mask whichever kernel path produced it
+    assert _rn.barrier_timeouts() == 0
 
 
 _DROPOUT_MASKS = []
@@ -988,10 +1020,14 @@ def test_group_norm_all_kernel_paths(dev, monkeypatch, mode, c, act, res):
         monkeypatch.setenv("RN_GN_NO_SLICE", "1")
     if mode in ("grid_resident", "three_kernel"):
         monkeypatch.setenv("RN_GN_NO_ROWS", "1")
+    if mode == "grid_resident":
+        monkeypatch.setattr(ops, "GN_GRID_RESIDENT", True)     # (off by default: without the sync region that path declines)
     if mode == "three_kernel":
         monkeypatch.setenv("RN_GN_NO_COOP", "1")
     rng = np.random.default_rng(c + len(mode))
     shapes = [(2, 40, 36, c), (2, 20, 18, c), (2, 3, 3, c)]
+    for path in _gn_paths(dev, shapes, c, act):
+        assert path in _GN_MODE_PATHS[mode], "mode %s runs the %s implementation" % (mode, path)
     gamma = (1 + 0.3 * rng.standard_normal(c)).astype(np.float32)
     beta = (0.2 * rng.standard_normal(c)).astype(np.float32)
     xs = [(rng.standard_normal(s) * 2 + 0.5).astype(np.float32) for s in shapes]
