@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 418
+#define RN_API_VERSION 419
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -671,7 +671,7 @@ int rn_train_metrics_pass(const rn_metrics_seg* segs, int nseg, int num_classes,
  *   int64   [5] steps  [6] nonfinite_steps  [7] tn  [8] fp  [9] fn  [10] tp  [11] iou_rows
  * The step is added ONLY IF class_loss, regr_loss, reg_loss and the step's IoU sum are all finite; otherwise nonfinite_steps
  * advances and nothing else changes (a degenerate box gives NaN as in the reference; one such step must not poison a window's
- * means).  The gate is the metric's own, independent of rn_finite_gate_eval.  Plain stores. */
+ * means).  The gate is the metric's own, independent of the guard's (RN_CTL_F_GUARD).  Plain stores. */
 #define RN_TRAIN_METRICS_STATE_BYTES 96
 int rn_train_metrics_fold(const void* workspace, size_t workspace_bytes, const float* class_loss, const float* regr_loss,
                           const float* reg_loss, void* state, rn_stream_t stream);
@@ -1030,9 +1030,9 @@ int rn_norm_reg_finalize(const double* partial, int64_t npairs, float* out2, rn_
  *   s >= W  RN_LR_CONSTANT lr = base_lr
  *           RN_LR_STEP     lr = base_lr * decay_factor ^ #{i : boundaries[i] <= s}
  *           RN_LR_COSINE   lr = base_lr * (ff + (1 - ff) * 0.5 * (1 + cos(pi * min(1, (s - W) / (T - W)))))
- * all in double, rounded to float once.  Checked by the entry: kind; warmup_steps >= 0; f0, ff in [0, 1]; n_boundaries in
+ * all in double, rounded to float once.  Checked by rn_step_control_eval: kind; warmup_steps >= 0; f0, ff in [0, 1]; n_boundaries in
  * [0, RN_LR_MAX_BOUNDARIES], boundaries >= 0 and strictly increasing; total_steps > warmup_steps (RN_LR_COSINE needs it; the
- * other kinds do not read it and also take 0 = unset). */
+ * other kinds do not read it and also take 0 = unset).  The rate is evaluated by rn_step_control_eval (RN_CTL_F_LR, below). */
 enum rn_lr_kind { RN_LR_CONSTANT = 0, RN_LR_STEP = 1, RN_LR_COSINE = 2 };
 #define RN_LR_MAX_BOUNDARIES 8
 typedef struct rn_lr_schedule {
@@ -1042,52 +1042,52 @@ typedef struct rn_lr_schedule {
   int64_t warmup_steps, total_steps;
   int64_t boundaries[RN_LR_MAX_BOUNDARIES];
 } rn_lr_schedule;
-/* One thread: s = *step_dev;  lr_dev[0] = lr(s);  lr_dev[1] = the rate the update kernel multiplies by -- for RN_OPT_ADAM
- * lr(s) * sqrt(1 - 0.999^t) / (1 - 0.9^t), t = s + 1, formed in double from the rounded lr(s) exactly as rn_optimizer_update forms
- * it from its float `lr`; lr(s) itself for the other kinds;  *step_dev = s + 1.  No argument changes from step to step. */
-int rn_lr_schedule_eval(rn_lr_schedule sched, uint64_t* step_dev, float* lr_dev, int optimizer_kind, rn_stream_t stream);
-/* An exponential moving average of the weights, kept by the pass that updates them (tf.train.ExponentialMovingAverage; the
- * reference, train.py:111-134, trains and evaluates the raw weights only).  With n = updates applied before this one and w' the
- * weight after it:
- *   d(n) = min(decay, (1 + n) / (10 + n))   warmup != 0
- *        = decay                            warmup == 0
- *   e   <- e - (e - w') * (1 - d(n))        in fp32, per element
- * One thread: n = *num_updates_dev;  ema_dev[0] = d(n);  ema_dev[1] = 1 - d(n), each formed in double and rounded to float once;
- * *num_updates_dev = n + 1.  The count is the average's own device word (a constant-rate step has no step word).  No argument
- * changes from step to step, so a replayed hipGraph advances the average by itself.  Checked by the entry: 0 < decay < 1,
- * non-null pointers. */
-int rn_ema_decay_eval(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, rn_stream_t stream);
-/* Gradient accumulation inside the captured step (the reference takes one optimizer step per batch, train.py:111-134; a larger
- * effective batch than fits in memory is the usual reason to sum the gradients of A batches first).  A = accumulate_steps; a
- * micro-step is one forward + backward pass, an update is applied on every A-th micro-step, from the MEAN of the last A gradients.
- * GroupNorm is per sample, so that mean is the gradient of the A-times-larger batch (but for the dropout masks, drawn per
- * micro-step).  The backward kernels overwrite a parameter's gradient slot, so the sum has an arena of its own, `acc`, kept by the
- * pass that reads the gradients anyway.
- * One thread: p = *micro_dev % A;  accum_dev[0] = p;  accum_dev[1] = (p == A - 1);  *micro_dev += 1.  No argument changes from
- * micro-step to micro-step, so ONE replayed hipGraph serves every phase.  Checked by the entry: A >= 1, non-null pointers. */
-int rn_accum_phase_eval(int32_t accumulate_steps, uint64_t* micro_dev, int32_t* accum_dev, rn_stream_t stream);
-/* rn_lr_schedule_eval / rn_ema_decay_eval behind the gate accum_dev[1] (what rn_accum_phase_eval left there): the same kernel
- * body and the same argument checks when it is non-zero; otherwise NOTHING -- lr_dev / ema_dev and the step / update word stay as
- * they are, so both count updates, not micro-steps.  accum_dev must not be null. */
-int rn_lr_schedule_eval_gated(rn_lr_schedule sched, uint64_t* step_dev, float* lr_dev, int optimizer_kind, const int32_t* accum_dev,
-                              rn_stream_t stream);
-int rn_ema_decay_eval_gated(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, const int32_t* accum_dev,
-                            rn_stream_t stream);
+/* THE STEP'S CONTROL WORDS: one one-thread launch ahead of the update forms every device word the update kernels read, so that no
+ * launch argument changes from step to step and a replayed hipGraph advances all of them by itself.  The descriptor lives in host
+ * memory, is read before the call returns and travels to the kernel by value.  `features` says which of the four parts run -- in
+ * this order -- and which fields are set; the fields of a clear feature stay 0 / null.
+ * RN_CTL_F_ACCUM  gradient accumulation (the reference takes one optimizer step per batch, train.py:111-134; a larger effective
+ *   batch than fits in memory is the usual reason to sum the gradients of A batches first).  A = accumulate_steps; a micro-step is
+ *   one forward + backward pass, an update is applied on every A-th one, from the MEAN of the last A gradients (GroupNorm is per
+ *   sample, so that is the gradient of the A-times-larger batch but for the dropout masks, drawn per micro-step).
+ *     p = *micro_dev % A;  accum_dev[0] = p;  accum_dev[1] = (p == A - 1);  *micro_dev += 1
+ * RN_CTL_F_GUARD  a guard against non-finite gradients (the reference trains on whatever its graph computes: a NaN regression
+ *   target from a ground-truth box of zero extent reaches every weight).  The criterion is the float rn_norm_reg_finalize leaves,
+ *   so the launch stands BEHIND it: sum g'^2 over the whole arena is not finite iff some g' is NaN or inf or the sum overflows.
+ *     f = isfinite(norm_sq[0]);  gate_dev[0] = 0;  gate_dev[1] = f;  f ? (skipped_dev[1] = 0) : (skipped_dev[0] += 1, skipped_dev[1] += 1)
+ *   so gate_dev has accum_dev's layout and skipped_dev = [updates skipped in all, updates skipped in a row].
+ * The two parts below run behind the gate accum_dev[1] (ACCUM) or gate_dev[1] (GUARD), always without either.  A closed gate
+ * leaves lr_dev, ema_dev, *step_dev and *ema_updates_dev as they are: both words, and Adam's bias correction, count APPLIED updates.
+ * RN_CTL_F_LR     s = *step_dev;  lr_dev[0] = lr(s) of `schedule` (above);  lr_dev[1] = the rate the update kernel multiplies by --
+ *   for optimizer_kind RN_OPT_ADAM lr(s) * sqrt(1 - 0.999^t) / (1 - 0.9^t), t = s + 1, formed in double from the rounded lr(s)
+ *   exactly as rn_optimizer_update forms it from its float `lr`; lr(s) itself for the other kinds;  *step_dev = s + 1.
+ * RN_CTL_F_EMA    an exponential moving average of the weights, kept by the pass that updates them
+ *   (tf.train.ExponentialMovingAverage; the reference trains and evaluates the raw weights only).  With n = updates applied before
+ *   this one and w' the weight after it:
+ *     d(n) = min(ema_decay, (1 + n) / (10 + n))   ema_warmup != 0
+ *          = ema_decay                            ema_warmup == 0
+ *     e   <- e - (e - w') * (1 - d(n))            in fp32, per element (RN_OPT_F_EMA)
+ *   n = *ema_updates_dev;  ema_dev[0] = d(n);  ema_dev[1] = 1 - d(n), each formed in double and rounded to float once;
+ *   *ema_updates_dev = n + 1.  The count is the average's own word (a constant-rate step has no step word).
+ * Checked before the launch, each RN_EINVAL with a message: non-null c; no unknown feature bit and at least one; never ACCUM with
+ * GUARD (one gate; rn_optimizer_update refuses the pair too); a known optimizer_kind; micro_dev and accum_dev both given iff ACCUM,
+ * accumulate_steps >= 1; norm_sq, gate_dev and skipped_dev all given iff GUARD, 4 / 4 / 8-byte aligned; step_dev and lr_dev both
+ * given iff LR, and the schedule's own list (above); ema_updates_dev and ema_dev both given iff EMA, 0 < ema_decay < 1. */
+enum rn_ctl_feature { RN_CTL_F_ACCUM = 1, RN_CTL_F_GUARD = 2, RN_CTL_F_LR = 4, RN_CTL_F_EMA = 8 };
+typedef struct rn_step_control {
+  uint32_t features; int32_t optimizer_kind;
+  int32_t accumulate_steps; uint64_t* micro_dev; int32_t* accum_dev;               /* ACCUM */
+  const float* norm_sq; int32_t* gate_dev; uint64_t* skipped_dev;                   /* GUARD */
+  rn_lr_schedule schedule; uint64_t* step_dev; float* lr_dev;                       /* LR    */
+  double ema_decay; int32_t ema_warmup; uint64_t* ema_updates_dev; float* ema_dev;  /* EMA   */
+} rn_step_control;
+int rn_step_control_eval(const rn_step_control* c, rn_stream_t stream);
 /* The norm pass of rn_grad_norm_l2reg for a SLICE [w, w + count) of the arena (wd_per_block points at the slice's first block):
  * rn_optimizer_norm_pairs(count) (double, double) pairs of (sum g'^2, L2 regulariser value) into `partial`, in the layout
  * RN_OPT_F_NORM writes; rn_norm_reg_finalize over the pairs of all slices gives [sum g'^2, reg].  The caller owns
  * `partial`: no workspace, nothing a capture may not contain. */
 int rn_grad_norm_partial(const float* w, const float* grad, const float* wd_per_block, int64_t count, float grad_scale,
                          double* partial, rn_stream_t stream);
-/* A guard against non-finite gradients inside the captured step (the reference trains on whatever its graph computes,
- * train.py:111-134: a NaN regression target from a ground-truth box of zero extent reaches every weight).  The criterion is the
- * float rn_norm_reg_finalize leaves: sum g'^2 over the whole arena is not finite iff some g' is NaN or inf or the sum overflows.
- * One thread: f = isfinite(norm_sq[0]);  gate_dev[0] = 0;  gate_dev[1] = f;  f ? (skipped_dev[1] = 0)
- * : (skipped_dev[0] += 1, skipped_dev[1] += 1), so skipped_dev = [updates skipped in all, updates skipped in a row].  gate_dev has
- * the layout of accum_dev: rn_lr_schedule_eval_gated and rn_ema_decay_eval_gated run behind it unchanged, and the step word, the
- * average's word and Adam's bias correction count APPLIED updates.  No argument changes from step to step.  Checked by the entry:
- * non-null pointers, norm_sq / gate_dev 4-byte and skipped_dev 8-byte aligned. */
-int rn_finite_gate_eval(const float* norm_sq, int32_t* gate_dev, uint64_t* skipped_dev, rn_stream_t stream);
 /* THE UPDATE: one pass over a slice [w, w + count) of the arena (wd_per_block points at the slice's first block), fp32 per element,
  * float4 accesses, 16 B/element for RN_OPT_MOMENTUM and 20 for the other kinds (w, grad, state1 [, state2] read; all but grad
  * written).  With g' as above, lr the rate and state1 / state2 = momentum-acc | rms, mom | m, v:
@@ -1104,18 +1104,18 @@ int rn_finite_gate_eval(const float* norm_sq, int32_t* gate_dev, uint64_t* skipp
  * RN_OPT_F_NORM   the pass also forms the slice's share of (sum g'^2, L2 regulariser value), both at the weights BEFORE the update
  *   (one read of w and grad instead of two): rn_optimizer_norm_pairs(count) pairs into `partial`.  No clipping then: the norm is
  *   not an input.  A trainer can so update the heads + FPN slice while the backbone's backward pass runs.
- * RN_OPT_F_LRDEV  the rate is lr_dev[1], what rn_lr_schedule_eval left there -- bias correction included -- instead of `lr`; `lr`
+ * RN_OPT_F_LRDEV  the rate is lr_dev[1], what rn_step_control_eval left there -- bias correction included -- instead of `lr`; `lr`
  *   and `step` are not read.  Same kernel, same grid, same `partial` layout.  Without it RN_OPT_ADAM needs step >= 1, an argument
  *   that DOES change from step to step.
  * RN_OPT_F_EMA    the pass also keeps the moving average `ema` (count floats, 16-byte aligned, laid out like w) with 1 - d(n) read
- *   from ema_dev[1], what rn_ema_decay_eval left there.  w, the slots, the pairs and the counter come out exactly as without it:
+ *   from ema_dev[1], what rn_step_control_eval left there.  w, the slots, the pairs and the counter come out exactly as without it:
  *   the average is one more load, one fused multiply-add and one more store per element (+8 B/element).
  * RN_OPT_F_CLIP   clip_scale = clip_norm / max(sqrt(norm_sq[0]), clip_norm), formed by the kernel from the device scalar, so
  *   nothing step-dependent is among the launch arguments and the clipped update can be a node of a captured step like the
  *   unclipped one.  The norm is an INPUT of this pass, so the pass before it forms it (rn_grad_norm_partial +
  *   rn_norm_reg_finalize, or rn_grad_norm_l2reg): never with NORM.  Without CLIP clip_norm is 0 and norm_sq null.
  * RN_OPT_F_ACCUM  (with NORM; never with CLIP or GATE) the update on an accumulated gradient.  Every wave reads accum_dev[0..1] =
- *   [p, applying], what rn_accum_phase_eval left there, once and the launch runs ONE of three loops, gs = grad_scale:
+ *   [p, applying], what rn_step_control_eval left there, once and the launch runs ONE of three loops, gs = grad_scale:
  *     p == 0, not applying   acc  = grad * gs                 acc is not read                              8 B/element
  *     p  > 0, not applying   acc += grad * gs                                                              12 B/element
  *     applying               G = (acc + grad * gs) * inv_accum;  g' = G + wd*w;  the update, the average and the (sum g'^2,
@@ -1125,9 +1125,9 @@ int rn_finite_gate_eval(const float* norm_sq, int32_t* gate_dev, uint64_t* skipp
  *   LAST update's (sum g'^2, regulariser) again.  advance_counter is bumped by every launch (fresh dropout masks per micro-step).
  *   acc: count floats, 16-byte aligned, laid out like w; zero-filled at the start.  inv_accum: the caller passes 1 / A.
  * RN_OPT_F_GATE   (never with NORM or ACCUM) the update behind the guard's gate: every wave reads gate_dev[1], what
- *   rn_finite_gate_eval left there, once; on 0 the launch bumps advance_counter (fresh dropout masks next step) and returns without
+ *   rn_step_control_eval left there, once; on 0 the launch bumps advance_counter (fresh dropout masks next step) and returns without
  *   touching w, the slots or ema; otherwise it is the ungated update, bit for bit.
- * A launch on another stream that reads lr_dev / ema_dev / accum_dev must be ordered behind the one-thread kernel that wrote it.
+ * A launch on another stream that reads lr_dev / ema_dev / accum_dev must be ordered behind the control launch that wrote it.
  * Checked before any launch, each RN_EINVAL with a message: non-null u, w, grad, state1, wd_per_block; count > 0 and whole
  * blocks; a known kind; state2 for RN_OPT_RMSPROP / RN_OPT_ADAM; no unknown feature bit; NORM with neither CLIP nor GATE; ACCUM
  * with NORM and with neither CLIP nor GATE; partial non-null iff NORM; lr_dev non-null iff LRDEV; ema and ema_dev both given iff

@@ -21,7 +21,8 @@ OPT_BLOCK = 1024
 LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
-API_VERSION = 418        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
+API_VERSION = 419        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -29,10 +30,19 @@ class RnError(RuntimeError):
 
 
 class LrSchedule(C.Structure):
-    """rn_lr_schedule (passed by value); built by train.LRSchedule.struct()."""
+    """rn_lr_schedule (a field of StepControl); built by train.LRSchedule.struct()."""
     _fields_ = [("kind", C.c_int32), ("n_boundaries", C.c_int32), ("base_lr", C.c_double), ("warmup_factor", C.c_double),
                 ("final_factor", C.c_double), ("decay_factor", C.c_double), ("warmup_steps", C.c_int64), ("total_steps", C.c_int64),
                 ("boundaries", C.c_int64 * LR_MAX_BOUNDARIES)]
+
+
+class StepControl(C.Structure):
+    """rn_step_control (passed by pointer, read before rn_step_control_eval returns): the fields of a clear feature stay 0 / None."""
+    _fields_ = [("features", C.c_uint32), ("optimizer_kind", C.c_int32),
+                ("accumulate_steps", C.c_int32), ("micro_dev", C.c_void_p), ("accum_dev", C.c_void_p),                          # ACCUM
+                ("norm_sq", C.c_void_p), ("gate_dev", C.c_void_p), ("skipped_dev", C.c_void_p),                                 # GUARD
+                ("schedule", LrSchedule), ("step_dev", C.c_void_p), ("lr_dev", C.c_void_p),                                     # LR
+                ("ema_decay", C.c_double), ("ema_warmup", C.c_int32), ("ema_updates_dev", C.c_void_p), ("ema_dev", C.c_void_p)]  # EMA
 
 
 class OptUpdate(C.Structure):
@@ -252,9 +262,7 @@ SYMBOLS = [
     "rn_mb_pointwise_bwd_rows", "rn_mb_pointwise_bwd_workspace", "rn_mb_pointwise_bwd",
     "rn_mb_depthwise_bwd_rows", "rn_mb_depthwise_bwd_workspace", "rn_mb_depthwise_bwd", "rn_set_mb_dw_taps", "rn_get_mb_dw_taps",
     "rn_debug_collective_standin", "rn_optimizer_norm_pairs", "rn_norm_reg_finalize",
-    "rn_lr_schedule_eval", "rn_ema_decay_eval",
-    "rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated",
-    "rn_grad_norm_partial", "rn_finite_gate_eval",
+    "rn_step_control_eval", "rn_grad_norm_partial",
     "rn_train_metrics_workspace", "rn_train_metrics_pass", "rn_train_metrics_fold", "rn_train_metrics_reset",
 ]
 
@@ -296,13 +304,8 @@ def lib():
         L.rn_optimizer_norm_pairs.restype = C.c_int64
         L.rn_optimizer_update.argtypes = [C.POINTER(OptUpdate), C.c_void_p]
         L.rn_norm_reg_finalize.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        L.rn_lr_schedule_eval.argtypes = [LrSchedule, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.rn_ema_decay_eval.argtypes = [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rn_accum_phase_eval.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rn_lr_schedule_eval_gated.argtypes = [LrSchedule, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.rn_ema_decay_eval_gated.argtypes = [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rn_step_control_eval.argtypes = [C.POINTER(StepControl), C.c_void_p]
         L.rn_grad_norm_partial.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
-        L.rn_finite_gate_eval.argtypes = [C.c_void_p] * 4
         L.rn_debug_collective_standin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p]
         L.rn_conv2d_stats_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.rn_conv2d_fwd_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -45,15 +45,15 @@ __global__ void norm_reg_finalize_kernel(const double* __restrict__ partial, int
 // NORM: the pass that applies the update also forms this launch's share of (sum g'^2, L2 regulariser value) -- both at the
 // weights BEFORE the update, as rn_grad_norm_l2reg does -- into partial[block] (no clipping then: the norm is not an input)
 // EMA: the pass also keeps the exponential moving average of the weights (tf.train.ExponentialMovingAverage): with w' the
-// weight this launch stores and om = ema_dev[1] = 1 - d(n), what rn_ema_decay_eval left on the device, e <- e - (e - w') * om.
+// weight this launch stores and om = ema_dev[1] = 1 - d(n), what rn_step_control_eval left on the device, e <- e - (e - w') * om.
 // The two EMA arguments are not read by the EMA = false instantiations.
 // ACC (RN_OPT_F_ACCUM): the pass sums the gradients of A launches in `acc` and applies their mean on the A-th.  Every wave
-// reads accum_dev = [p, applying], what rn_accum_phase_eval left on the device, once (a uniform load, like lr_dev[1]) and runs ONE
+// reads accum_dev = [p, applying], what rn_step_control_eval left on the device, once (a uniform load, like lr_dev[1]) and runs ONE
 // of three loops: p == 0 and not applying, acc = g * gs (acc is not read); 0 < p and not applying, acc += g * gs; applying, the
 // update from G = (acc + g * gs) * inv_accum in the place of g * gs (acc is not written: the next cycle's first launch overwrites
 // it).  The two accumulating loops touch nothing but acc and leave the block's `partial` pair as the last update wrote it; the
 // dropout counter advances in every launch.  The three accumulation arguments are not read by the ACC = false instantiations.
-// GATE (RN_OPT_F_GATE; never with ACC): `accum_dev` carries gate_dev = [0, finite], what rn_finite_gate_eval left on the
+// GATE (RN_OPT_F_GATE; never with ACC): `accum_dev` carries gate_dev = [0, finite], what rn_step_control_eval left on the
 // device in accum_dev's layout.  Every wave reads its second word once (a uniform load, like lr_dev[1]); on 0 the launch returns
 // behind the dropout counter's bump and touches neither w nor the slots nor ema.  No argument was added for it: the argument
 // block, and with it the code of the GATE = false instantiations, is what it was without the parameter.
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(T) void opt_step_kernel(float* __restrict__ w, cons
                                                      float* __restrict__ acc, float inv_accum, const int* __restrict__ accum_dev) {
   __shared__ double red[2][T / 64];
   double n2 = 0.0, rg = 0.0;
-  if (lr_dev) lr = lr_dev[1];  // the rate rn_lr_schedule_eval left on the device: one uniform load per wave, ahead of the loop
+  if (lr_dev) lr = lr_dev[1];  // the rate rn_step_control_eval left on the device: one uniform load per wave, ahead of the loop
   float om = 0.f;
   if (EMA) om = ema_dev[1];  // 1 - d(n) of this update, likewise
   if (advance && blockIdx.x == 0 && threadIdx.x == 0) *advance += advance_by;  // the step counter the dropout masks hash (fresh masks next step)
@@ -257,7 +257,7 @@ extern "C" int rn_optimizer_update(const rn_opt_update* u, rn_stream_t stream) {
 }
 
 namespace {
-// d(n) of rn_ema_decay_eval (include/rn_hip.h) and its complement, each formed in double and rounded to float once
+// d(n) of the EMA feature of rn_step_control (include/rn_hip.h) and its complement, each formed in double and rounded to float once
 __device__ void ema_decay_eval(double decay, int warmup, unsigned long long* num_updates_dev, float* ema_dev) {
   const unsigned long long n = *num_updates_dev;
   double d = decay;
@@ -267,42 +267,6 @@ __device__ void ema_decay_eval(double decay, int warmup, unsigned long long* num
   *num_updates_dev = n + 1;
 }
 
-__global__ void ema_decay_eval_kernel(double decay, int warmup, unsigned long long* num_updates_dev, float* ema_dev) {
-  ema_decay_eval(decay, warmup, num_updates_dev, ema_dev);
-}
-
-// gated (gradient accumulation): only the launch that applies an update -- accum_dev[1] != 0 -- advances the average's word
-__global__ void ema_decay_eval_gated_kernel(double decay, int warmup, unsigned long long* num_updates_dev, float* ema_dev,
-                                            const int* accum_dev) {
-  if (accum_dev[1] != 0) ema_decay_eval(decay, warmup, num_updates_dev, ema_dev);
-}
-
-int check_ema_decay_eval(double decay, const uint64_t* num_updates_dev, const float* ema_dev) {
-  RN_CHECK_ARG(num_updates_dev && ema_dev, "ema_decay_eval: null pointer");
-  RN_CHECK_ARG(decay > 0.0 && decay < 1.0, "ema_decay_eval: decay %g outside (0, 1)", decay);
-  return RN_OK;
-}
-}  // namespace
-
-extern "C" int rn_ema_decay_eval(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, rn_stream_t stream) {
-  if (int rc = check_ema_decay_eval(decay, num_updates_dev, ema_dev)) return rc;
-  hipLaunchKernelGGL(ema_decay_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, decay, warmup, (unsigned long long*)num_updates_dev,
-                     ema_dev);
-  RN_LAUNCH_CHECK();
-  return RN_OK;
-}
-
-extern "C" int rn_ema_decay_eval_gated(double decay, int warmup, uint64_t* num_updates_dev, float* ema_dev, const int32_t* accum_dev,
-                                       rn_stream_t stream) {
-  if (int rc = check_ema_decay_eval(decay, num_updates_dev, ema_dev)) return rc;
-  RN_CHECK_ARG(accum_dev, "ema_decay_eval_gated: null accum_dev");
-  hipLaunchKernelGGL(ema_decay_eval_gated_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, decay, warmup,
-                     (unsigned long long*)num_updates_dev, ema_dev, (const int*)accum_dev);
-  RN_LAUNCH_CHECK();
-  return RN_OK;
-}
-
-namespace {
 // lr(s) of rn_lr_schedule (include/rn_hip.h), in double; the caller rounds it to float once
 __device__ double lr_schedule_value(const rn_lr_schedule& d, uint64_t s) {
   const double base = d.base_lr;
@@ -333,94 +297,82 @@ __device__ void lr_schedule_eval(const rn_lr_schedule& d, unsigned long long* st
   *step_dev = s + 1;
 }
 
-__global__ void lr_schedule_eval_kernel(rn_lr_schedule d, unsigned long long* step_dev, float* lr_dev, int opt_kind) {
-  lr_schedule_eval(d, step_dev, lr_dev, opt_kind);
+// The step's control words, one thread: the phase or the finite gate first (never both), then the schedule and the average's
+// decay behind the gate either of them left -- a closed gate leaves lr_dev, ema_dev and the two words they count in untouched.
+//   accum_dev   = [p, p == A - 1], p = micro-steps seen so far mod A; the word advances
+//   gate_dev    = [0, sum g'^2 finite]: accum_dev's layout (opt_step_kernel reads either through one argument)
+//   skipped_dev = [updates skipped in all, updates skipped in a row] (the second word starts again at an applied update)
+__global__ void step_control_kernel(rn_step_control c) {
+  int gate = 1;
+  if (c.features & RN_CTL_F_ACCUM) {
+    unsigned long long* micro_dev = (unsigned long long*)c.micro_dev;
+    const unsigned long long m = *micro_dev;
+    const int p = (int)(m % (unsigned long long)c.accumulate_steps);
+    gate = (p == c.accumulate_steps - 1) ? 1 : 0;
+    c.accum_dev[0] = p;
+    c.accum_dev[1] = gate;
+    *micro_dev = m + 1;
+  }
+  if (c.features & RN_CTL_F_GUARD) {
+    unsigned long long* skipped_dev = (unsigned long long*)c.skipped_dev;
+    const bool finite = isfinite(c.norm_sq[0]);
+    gate = finite ? 1 : 0;
+    c.gate_dev[0] = 0;
+    c.gate_dev[1] = gate;
+    if (finite) {
+      skipped_dev[1] = 0ull;
+    } else {
+      skipped_dev[0] += 1ull;
+      skipped_dev[1] += 1ull;
+    }
+  }
+  if (!gate) return;
+  if (c.features & RN_CTL_F_LR) lr_schedule_eval(c.schedule, (unsigned long long*)c.step_dev, c.lr_dev, c.optimizer_kind);
+  if (c.features & RN_CTL_F_EMA) ema_decay_eval(c.ema_decay, c.ema_warmup, (unsigned long long*)c.ema_updates_dev, c.ema_dev);
 }
 
-// gated (gradient accumulation): only the launch that applies an update -- accum_dev[1] != 0 -- evaluates and advances the schedule
-__global__ void lr_schedule_eval_gated_kernel(rn_lr_schedule d, unsigned long long* step_dev, float* lr_dev, int opt_kind,
-                                              const int* accum_dev) {
-  if (accum_dev[1] != 0) lr_schedule_eval(d, step_dev, lr_dev, opt_kind);
-}
-
-int check_lr_schedule_eval(const rn_lr_schedule& d, const uint64_t* step_dev, const float* lr_dev, int optimizer_kind) {
-  RN_CHECK_ARG(step_dev && lr_dev, "lr_schedule_eval: null pointer");
-  RN_CHECK_ARG(optimizer_kind == RN_OPT_MOMENTUM || optimizer_kind == RN_OPT_RMSPROP || optimizer_kind == RN_OPT_ADAM,
-               "lr_schedule_eval: unknown optimizer kind %d", optimizer_kind);
-  RN_CHECK_ARG(d.kind == RN_LR_CONSTANT || d.kind == RN_LR_STEP || d.kind == RN_LR_COSINE, "lr_schedule_eval: unknown kind %d", d.kind);
-  RN_CHECK_ARG(d.warmup_steps >= 0, "lr_schedule_eval: warmup_steps %lld < 0", (long long)d.warmup_steps);
+int check_lr_schedule(const rn_lr_schedule& d) {
+  RN_CHECK_ARG(d.kind == RN_LR_CONSTANT || d.kind == RN_LR_STEP || d.kind == RN_LR_COSINE, "step_control: unknown schedule kind %d", d.kind);
+  RN_CHECK_ARG(d.warmup_steps >= 0, "step_control: warmup_steps %lld < 0", (long long)d.warmup_steps);
   RN_CHECK_ARG(d.warmup_factor >= 0.0 && d.warmup_factor <= 1.0 && d.final_factor >= 0.0 && d.final_factor <= 1.0,
-               "lr_schedule_eval: warmup_factor %g / final_factor %g outside [0, 1]", d.warmup_factor, d.final_factor);
-  RN_CHECK_ARG(d.n_boundaries >= 0 && d.n_boundaries <= RN_LR_MAX_BOUNDARIES, "lr_schedule_eval: %d boundaries, at most %d",
+               "step_control: warmup_factor %g / final_factor %g outside [0, 1]", d.warmup_factor, d.final_factor);
+  RN_CHECK_ARG(d.n_boundaries >= 0 && d.n_boundaries <= RN_LR_MAX_BOUNDARIES, "step_control: %d boundaries, at most %d",
                d.n_boundaries, RN_LR_MAX_BOUNDARIES);
   for (int i = 0; i < d.n_boundaries; ++i)
     RN_CHECK_ARG(d.boundaries[i] >= 0 && (i == 0 || d.boundaries[i] > d.boundaries[i - 1]),
-                 "lr_schedule_eval: boundaries must be non-negative and strictly increasing (entry %d)", i);
+                 "step_control: boundaries must be non-negative and strictly increasing (entry %d)", i);
   RN_CHECK_ARG(d.total_steps > d.warmup_steps || (d.kind != RN_LR_COSINE && d.total_steps == 0),
-               "lr_schedule_eval: total_steps %lld is not above warmup_steps %lld", (long long)d.total_steps, (long long)d.warmup_steps);
+               "step_control: total_steps %lld is not above warmup_steps %lld", (long long)d.total_steps, (long long)d.warmup_steps);
   return RN_OK;
 }
 }  // namespace
 
-extern "C" int rn_lr_schedule_eval(rn_lr_schedule d, uint64_t* step_dev, float* lr_dev, int optimizer_kind, rn_stream_t stream) {
-  if (int rc = check_lr_schedule_eval(d, step_dev, lr_dev, optimizer_kind)) return rc;
-  hipLaunchKernelGGL(lr_schedule_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d, (unsigned long long*)step_dev, lr_dev, optimizer_kind);
-  RN_LAUNCH_CHECK();
-  return RN_OK;
-}
-
-extern "C" int rn_lr_schedule_eval_gated(rn_lr_schedule d, uint64_t* step_dev, float* lr_dev, int optimizer_kind,
-                                         const int32_t* accum_dev, rn_stream_t stream) {
-  if (int rc = check_lr_schedule_eval(d, step_dev, lr_dev, optimizer_kind)) return rc;
-  RN_CHECK_ARG(accum_dev, "lr_schedule_eval_gated: null accum_dev");
-  hipLaunchKernelGGL(lr_schedule_eval_gated_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d, (unsigned long long*)step_dev, lr_dev,
-                     optimizer_kind, (const int*)accum_dev);
-  RN_LAUNCH_CHECK();
-  return RN_OK;
-}
-
-namespace {
-// p = micro-steps seen so far mod A: accum_dev = [p, p == A - 1] for this launch's kernels, and the word advances
-__global__ void accum_phase_eval_kernel(int accumulate_steps, unsigned long long* micro_dev, int* accum_dev) {
-  const unsigned long long m = *micro_dev;
-  const int p = (int)(m % (unsigned long long)accumulate_steps);
-  accum_dev[0] = p;
-  accum_dev[1] = (p == accumulate_steps - 1) ? 1 : 0;
-  *micro_dev = m + 1;
-}
-}  // namespace
-
-extern "C" int rn_accum_phase_eval(int32_t accumulate_steps, uint64_t* micro_dev, int32_t* accum_dev, rn_stream_t stream) {
-  RN_CHECK_ARG(micro_dev && accum_dev, "accum_phase_eval: null pointer");
-  RN_CHECK_ARG(accumulate_steps >= 1, "accum_phase_eval: accumulate_steps %d < 1", (int)accumulate_steps);
-  hipLaunchKernelGGL(accum_phase_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int)accumulate_steps,
-                     (unsigned long long*)micro_dev, (int*)accum_dev);
-  RN_LAUNCH_CHECK();
-  return RN_OK;
-}
-
-namespace {
-// gate_dev = [0, sum g'^2 finite]: the layout of accum_dev, so that the gated one-thread kernels above run behind it as they are;
-// skipped_dev = [updates skipped in all, updates skipped in a row] (the second word starts again at an applied update)
-__global__ void finite_gate_eval_kernel(const float* norm_sq, int* gate_dev, unsigned long long* skipped_dev) {
-  const bool finite = isfinite(norm_sq[0]);
-  gate_dev[0] = 0;
-  gate_dev[1] = finite ? 1 : 0;
-  if (finite) {
-    skipped_dev[1] = 0ull;
-  } else {
-    skipped_dev[0] += 1ull;
-    skipped_dev[1] += 1ull;
-  }
-}
-}  // namespace
-
-extern "C" int rn_finite_gate_eval(const float* norm_sq, int32_t* gate_dev, uint64_t* skipped_dev, rn_stream_t stream) {
-  RN_CHECK_ARG(norm_sq && gate_dev && skipped_dev, "finite_gate_eval: null pointer");
-  RN_CHECK_ARG(((uintptr_t)norm_sq & 3) == 0 && ((uintptr_t)gate_dev & 3) == 0 && ((uintptr_t)skipped_dev & 7) == 0,
-               "finite_gate_eval: misaligned pointer (norm_sq 4, gate_dev 4, skipped_dev 8 bytes)");
-  hipLaunchKernelGGL(finite_gate_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, norm_sq, (int*)gate_dev,
-                     (unsigned long long*)skipped_dev);
+// The one control entry: `features` says which words the launch forms and which fields must be set -- a pointer that is null (or
+// set) by mistake is refused, it does not select another behaviour.  Every check stands ahead of the launch.
+extern "C" int rn_step_control_eval(const rn_step_control* c, rn_stream_t stream) {
+  RN_CHECK_ARG(c, "step_control: null descriptor");
+  const uint32_t f = c->features;
+  const bool accum = f & RN_CTL_F_ACCUM, guard = f & RN_CTL_F_GUARD, lr = f & RN_CTL_F_LR, ema = f & RN_CTL_F_EMA;
+  RN_CHECK_ARG(!(f & ~(uint32_t)(RN_CTL_F_ACCUM | RN_CTL_F_GUARD | RN_CTL_F_LR | RN_CTL_F_EMA)), "step_control: unknown feature bit in 0x%x",
+               (unsigned)f);
+  RN_CHECK_ARG(f != 0, "step_control: no feature set, nothing to launch");
+  RN_CHECK_ARG(!(accum && guard), "step_control: ACCUM goes with no GUARD: the schedule and the average run behind ONE gate");
+  RN_CHECK_ARG((c->micro_dev != nullptr) == accum && (c->accum_dev != nullptr) == accum,
+               "step_control: micro_dev and accum_dev go together, with ACCUM and only with it");
+  RN_CHECK_ARG(!accum || c->accumulate_steps >= 1, "step_control: accumulate_steps %d < 1", (int)c->accumulate_steps);
+  RN_CHECK_ARG((c->norm_sq != nullptr) == guard && (c->gate_dev != nullptr) == guard && (c->skipped_dev != nullptr) == guard,
+               "step_control: norm_sq, gate_dev and skipped_dev go together, with GUARD and only with it");
+  RN_CHECK_ARG(((uintptr_t)c->norm_sq & 3) == 0 && ((uintptr_t)c->gate_dev & 3) == 0 && ((uintptr_t)c->skipped_dev & 7) == 0,
+               "step_control: misaligned pointer (norm_sq 4, gate_dev 4, skipped_dev 8 bytes)");
+  RN_CHECK_ARG((c->step_dev != nullptr) == lr && (c->lr_dev != nullptr) == lr, "step_control: step_dev and lr_dev go together, with LR and only with it");
+  RN_CHECK_ARG(c->optimizer_kind == RN_OPT_MOMENTUM || c->optimizer_kind == RN_OPT_RMSPROP || c->optimizer_kind == RN_OPT_ADAM,
+               "step_control: unknown optimizer kind %d", (int)c->optimizer_kind);
+  if (lr)
+    if (int rc = check_lr_schedule(c->schedule)) return rc;
+  RN_CHECK_ARG((c->ema_updates_dev != nullptr) == ema && (c->ema_dev != nullptr) == ema,
+               "step_control: ema_updates_dev and ema_dev go together, with EMA and only with it");
+  RN_CHECK_ARG(!ema || (c->ema_decay > 0.0 && c->ema_decay < 1.0), "step_control: ema_decay %g outside (0, 1)", c->ema_decay);
+  hipLaunchKernelGGL(step_control_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, *c);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }

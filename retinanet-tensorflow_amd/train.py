@@ -82,7 +82,7 @@ class LRSchedule(object):
                 step       base * decay_factor ** #{boundaries b <= s}
                 cosine     base * (ff + (1 - ff) * 0.5 * (1 + cos(pi * min(1, (s - W) / (T - W)))))
 
-    in float64, rounded to float32 once.  rn_lr_schedule_eval evaluates the same descriptor on the device (struct()), where a
+    in float64, rounded to float32 once.  rn_step_control_eval evaluates the same descriptor on the device (struct()), where a
     replayed graph advances it by itself; value(s) is the host's copy of the formula (launch arguments of a CPU arena's update,
     logging, tests).  Immutable and hashable: it is part of the one-graph step's cache key."""
 
@@ -149,7 +149,7 @@ class LRSchedule(object):
         return np.float32(lr)
 
     def struct(self):
-        """The descriptor rn_lr_schedule_eval takes by value (rn_lr_schedule of include/rn_hip.h)."""
+        """rn_lr_schedule of include/rn_hip.h: the `schedule` field of rn_step_control."""
         kind, base, W, f0, bounds, decay, T, ff = self._key
         d = _rn.LrSchedule(kind=self.KINDS.index(kind), n_boundaries=len(bounds), base_lr=base, warmup_factor=f0,
                            final_factor=ff, decay_factor=decay, warmup_steps=W, total_steps=T or 0)
@@ -159,55 +159,38 @@ class LRSchedule(object):
 
 
 class Optimizer(object):
-    """tf.train.MomentumOptimizer(lr, 0.9) | RMSPropOptimizer(lr, 0.9, 0.9) | AdamOptimizer(lr)
-    (train.py:114-119) + optional tf.clip_by_global_norm (train.py:127-132), one fused kernel.
+    """tf.train.MomentumOptimizer(lr, 0.9) | RMSPropOptimizer(lr, 0.9, 0.9) | AdamOptimizer(lr) (train.py:114-119) + optional
+    tf.clip_by_global_norm (train.py:127-132) on the flat arena.  Every configuration takes ONE sequence per call of step():
 
-    `grad_clip_norm` C (device arena): the norm is an input of the clipped update, so step() runs one more pass over w and g ahead
-    of it -- rn_grad_norm_partial into `_partial`, rn_norm_reg_finalize into `norm_reg` -- and the update (RN_OPT_F_CLIP) forms
-    C / max(sqrt(norm_reg[0]), C) from the device scalar itself (_step_clipped).  Rate, bias correction and the average's decay are
-    read from the device exactly as without clipping: the clipped update is recorded into a captured step like the unclipped one.
-    Only a CPU arena (or RN_FUSED_OPT_NORM=0) keeps rn_grad_norm_l2reg + rn_optimizer_update without RN_OPT_F_LRDEV: the rate
-    is a launch argument.  Which features an optimizer's updates carry follows from its constructor's arguments: `_features`.
+        count_step     the host's count of updates
+        norm ahead     rn_grad_norm_partial + rn_norm_reg_finalize -> norm_reg, where the norm is an INPUT of what follows:
+                       grad_clip_norm (RN_OPT_F_CLIP) and skip_nonfinite (RN_OPT_F_GATE); one more pass over w and g
+        control        ONE rn_step_control_eval, built once here (`_control`; None: no launch): every device word the update reads
+        update         rn_optimizer_update with `_features`, over the arena or per slice (step_slice)
+        finalize       rn_norm_reg_finalize -> norm_reg, where the update formed the norm beside itself (RN_OPT_F_NORM)
 
-    `schedule` (LRSchedule): the rate of update s is schedule.value(s); `lr` stays the base rate.  On a device arena the rate never
-    passes through the host, with and without clipping: begin_step launches rn_lr_schedule_eval, which reads the device step word
-    `step_dev`, leaves [lr(s), the rate the update multiplies by] in `lr_dev` and advances the word; the slices' update kernels read
-    lr_dev[1].  No launch argument of such a step changes from one step to the next, Adam's bias correction included.
+    begin_step is the first three, step_slice the update, finish_step the rest.  Nothing in it allocates, synchronises or reads a
+    device value, and on a device arena no launch argument changes from step to step -- but Adam's / RMSProp's rate without a
+    schedule (Trainer._whole_step_ok) -- so the sequence is recorded into the one-graph step as it is launched eagerly.
 
-    `ema_decay` D (0 < D < 1; device arena): `ema` holds an exponential moving average of the weights with
-    tf.train.ExponentialMovingAverage's semantics, kept by the update kernel itself -- with n = updates applied before this one and
-    w' the weight after it, e <- e - (e - w') * (1 - d(n)), d(n) = min(D, (1 + n) / (10 + n)) (`ema_warmup`) or D.  n is the
-    average's own device word `ema_updates_dev`: begin_step launches rn_ema_decay_eval, which leaves [d(n), 1 - d(n)] in `ema_dev`
-    and advances the word, so this too adds no launch argument that changes from step to step.
+    What the control launch keeps, each behind its constructor argument (formulas: include/rn_hip.h, rn_step_control):
+      `schedule` (LRSchedule)  lr_dev = [lr(s), the rate the update multiplies by: Adam's bias correction included] from the step
+        word step_dev, which it advances.  `lr` stays the base rate; current_lr() is the host's copy.
+      `ema_decay` D in (0, 1), `ema_warmup`  ema_dev = [d(n), 1 - d(n)] from the average's own word ema_updates_dev; the update keeps
+        `ema`, tf.train.ExponentialMovingAverage of the weights, in the same pass.
+      `accumulate_steps` A > 1 (no clipping, no guard)  accum_dev = [p, p == A - 1] from the micro-step word micro_dev.  step() is a
+        MICRO-step: the update sums the gradient into `acc` (+4 B per parameter) and applies the mean on every A-th one.  On a
+        micro-step that only sums, norm_reg keeps the last update's values; the dropout counter advances every micro-step.
+      `skip_nonfinite`  gate_dev = [0, norm_reg[0] finite] and skipped_dev = [updates skipped in all, in a row].  A skipped update
+        leaves w, the slots, ema and every word of the schedule and the average bit-untouched; the dropout counter advances and
+        norm_reg shows the offending norm.  With several ranks the norm is the reduced gradient's: all ranks decide alike.
+    Schedule and average run behind the phase's or the guard's gate, so step_count, step_dev, ema_updates_dev and Adam's bias
+    correction count APPLIED updates.  The host never reads a device word inside a step: under the guard step_count runs ahead by
+    the skips it has not seen until reconcile_skips() (which synchronises) subtracts them.  Guarded Adam / RMSProp given no
+    schedule get LRSchedule('constant', learning_rate), so that the bias correction counts on the device.
 
-    `accumulate_steps` A (an integer >= 1, default 1; A > 1: device arena, no clipping): gradient accumulation.  A call of step()
-    is a MICRO-step; an update is applied on every A-th one, from the mean of the last A gradients (each already times grad_scale).
-    The backward kernels overwrite a parameter's gradient slot, so the sum lives in an arena of its own, `acc` (+4 B per parameter),
-    kept by the update kernel: begin_step launches rn_accum_phase_eval, which leaves [p, p == A - 1] in `accum_dev` from the device
-    word `micro_dev` (p = micro-steps so far mod A) and advances the word; the update (RN_OPT_F_ACCUM) reads the pair and either only
-    sums (acc = g or acc += g: 8 / 12 B per element, nothing else touched) or applies (acc + g) / A (+4 B per element over the plain
-    update).  The schedule's and the average's one-thread kernels run behind the same gate, so `step_count`, `step_dev`,
-    `ema_updates_dev`, Adam's bias correction and current_lr() all count UPDATES.  On a micro-step that only sums, `norm_reg` (and
-    regularization_loss) keep the last update's values.  The dropout counter advances every micro-step.  Again no launch argument
-    changes from one micro-step to the next: one captured graph serves every phase.  With A = 1 none of this is allocated or launched.
-
-    `skip_nonfinite` (default False; device arena, accumulate_steps = 1): a guard.  Every step runs the norm pass over the whole
-    arena ahead of the update (_step_guarded) -- the pass the clipped update runs anyway; without clipping it is one more pass,
-    8 B per parameter -- and the update of a step is SKIPPED iff norm_reg[0], the float rn_norm_reg_finalize leaves, is not finite:
-    a NaN or an inf anywhere in the gradient, or a sum of squares that overflows a float.  rn_finite_gate_eval turns the float into
-    the int32 pair `gate_dev` = [0, finite] and keeps `skipped_dev` = [updates skipped in all, updates skipped in a row]; the
-    schedule's and the average's one-thread kernels and the update (RN_OPT_F_GATE) run behind that gate.  A skipped
-    update leaves the optimizer as if the step had not been taken: w, state1, state2, ema, step_dev, lr_dev, ema_updates_dev and
-    ema_dev keep their bits, and Adam's bias correction counts APPLIED updates.  What does change: the dropout counter advances
-    (fresh masks next step), norm_reg holds the offending step's values (the log shows the non-finite norm) and skipped_dev
-    advances.  Bias correction can count applied updates only on the device, so guarded Adam and RMSProp given no schedule read
-    their rate from the device too (an LRSchedule('constant', learning_rate) built here): a side effect is that they become
-    one-graph steps at a constant rate.  The host never reads a device word inside a step: step_count stays "updates applied" but
-    runs AHEAD by the skips the host has not seen until reconcile_skips() (which synchronises; the training loop calls it where
-    it synchronises anyway, at its log line and at a checkpoint) subtracts them, so between reconciles current_lr() is a log
-    value, not the rate the device applies.  With several ranks the norm is that of the REDUCED gradient: a NaN on any rank
-    reaches every rank's sum, so all ranks take the same decision with no extra collective.  With the guard off none of this is
-    allocated or launched and every path is what it was."""
+    A CPU arena or RN_FUSED_OPT_NORM=0 is the same sequence with the norm ahead from rn_grad_norm_l2reg (its own workspace and
+    summation order) and the rate a launch argument evaluated on the host: no schedule part in the control launch."""
 
     def __init__(self, arena, kind='momentum', learning_rate=1e-2, grad_clip_norm=None, schedule=None, ema_decay=None,
                  ema_warmup=True, accumulate_steps=1, skip_nonfinite=False):
@@ -239,11 +222,10 @@ class Optimizer(object):
             assert isinstance(schedule, LRSchedule)
             self.lr = schedule.base_lr
         # allocated HERE like _partial below (a lazy zero-fill inside a step would not be ordered against a side stream's slice)
-        self.step_dev = self.lr_dev = self._sched_struct = self._sched_event = None
+        self.step_dev = self.lr_dev = None
         if schedule is not None and dev.type == 'cuda':
             self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)        # (the kernel's uint64: same bits)
             self.lr_dev = torch.zeros(2, dtype=torch.float32, device=dev)
-            self._sched_struct = schedule.struct()
         # the moving average and its two device words: HERE as well, for the same reason (e starts as the weights as they are now)
         self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
         self.ema = self.ema_updates_dev = self.ema_dev = None
@@ -279,22 +261,39 @@ class Optimizer(object):
             self.gate_dev = torch.zeros(2, dtype=torch.int32, device=dev)
             self.skipped_dev = torch.zeros(2, dtype=torch.int64, device=dev)        # (the kernel's uint64 pair: same bits)
         # the path is fixed by now (step): behind the gate | the norm beside the update | the norm ahead of it (clipped, or not fused)
-        fused = dev.type == 'cuda' and FUSED_OPT_NORM
+        fused = self._fused = dev.type == 'cuda' and FUSED_OPT_NORM
         self._features = ((_rn.OPT_F_GATE if self.skip_nonfinite else _rn.OPT_F_NORM if fused and self.clip <= 0.0 else 0)
                           | (_rn.OPT_F_CLIP if self.clip > 0.0 else 0)
                           | (_rn.OPT_F_LRDEV if fused and self.lr_dev is not None else 0)   # (not fused: the host evaluates the schedule)
                           | (_rn.OPT_F_EMA if self.ema is not None else 0) | (_rn.OPT_F_ACCUM if self.acc is not None else 0))
+        # ... and so is the control launch: nothing in its descriptor changes from step to step (None: nothing to launch)
+        c = _rn.StepControl(optimizer_kind=_rn.OPT[kind])
+        if self.acc is not None:
+            c.features |= _rn.CTL_F_ACCUM
+            c.accumulate_steps, c.micro_dev, c.accum_dev = self.accumulate_steps, self.micro_dev.data_ptr(), self.accum_dev.data_ptr()
+        if self.skip_nonfinite:
+            c.features |= _rn.CTL_F_GUARD
+            c.norm_sq, c.gate_dev, c.skipped_dev = _rn.f32(self.norm_reg), self.gate_dev.data_ptr(), self.skipped_dev.data_ptr()
+        if self._features & _rn.OPT_F_LRDEV:
+            c.features |= _rn.CTL_F_LR
+            c.schedule, c.step_dev, c.lr_dev = schedule.struct(), self.step_dev.data_ptr(), _rn.f32(self.lr_dev)
+        if self.ema is not None:
+            c.features |= _rn.CTL_F_EMA
+            c.ema_decay, c.ema_warmup = self.ema_decay, int(self.ema_warmup)
+            c.ema_updates_dev, c.ema_dev = self.ema_updates_dev.data_ptr(), _rn.f32(self.ema_dev)
+        self._control = c if c.features else None
+        self._control_event = None      # behind the control launch: what a slice on a side stream waits for
         self.step_count = 0
 
-    def _update(self, lo, hi, grad_scale, advance_counter, partial=None, stream=None, lr=None, step=None):
+    def _update(self, lo, hi, grad_scale, advance_counter, partial=None, stream=None):
         """rn_optimizer_update over [lo, hi) of the arena with this optimizer's features; only the fields of set features are filled.
-        `lr` / `step` default to the base rate and the 1-based number of the update begin_step counted (Adam's bias correction):
-        both are read only without RN_OPT_F_LRDEV."""
+        `lr` / `step` are what begin_step left: this update's rate from the host and its 1-based number (Adam's bias correction),
+        both read only without RN_OPT_F_LRDEV."""
         a, f = self.arena, self._features
         u = _rn.OptUpdate(kind=_rn.OPT[self.kind], features=f, w=a.weights[lo:].data_ptr(), grad=a.grads[lo:].data_ptr(),
                           state1=self.state1[lo:].data_ptr(), state2=self.state2[lo:].data_ptr() if self.state2 is not None else None,
                           wd_per_block=a.wd_per_block[lo // OPT_BLOCK:].data_ptr(), count=hi - lo,
-                          lr=self.lr if lr is None else lr, grad_scale=grad_scale, step=self._update_no if step is None else step,
+                          lr=self._host_lr, grad_scale=grad_scale, step=self._update_no,
                           advance_counter=advance_counter.data_ptr() if advance_counter is not None else None,
                           advance_by=ops.DROPOUT_COUNTER_STEP)
         if f & _rn.OPT_F_NORM:
@@ -324,79 +323,11 @@ class Optimizer(object):
         return applying
 
     def step(self, grad_scale=1.0, advance_counter=None):
-        """`advance_counter`: the device word the dropout masks hash; bumped by the optimizer kernel itself."""
-        a = self.arena
-        if self.skip_nonfinite:
-            self._step_guarded(grad_scale, advance_counter)
-            return
-        if self.clip <= 0.0 and a.weights.is_cuda and FUSED_OPT_NORM:
-            # no clipping: the norm is not an input of the update -- one pass over the arena forms it beside the update
-            self.begin_step()
-            self.step_slice(0, a.count, grad_scale, advance_counter)
-            self.finish_step()
-            return
-        if a.weights.is_cuda and FUSED_OPT_NORM:
-            self._step_clipped(grad_scale, advance_counter)
-            return
-        # a CPU arena or RN_FUSED_OPT_NORM=0: the norm pass sizes its own workspace and the rate is a launch argument
-        L_ = _rn.lib()
-        ws = _rn.workspace(L_.rn_optimizer_workspace(a.count), a.weights.device)
-        _rn.check(L_.rn_grad_norm_l2reg(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count,
-                                        grad_scale, _rn.f32(self.norm_reg), ws.data_ptr(), ws.numel(), _rn.stream()),
-                  'rn_grad_norm_l2reg')
-        lr = self.current_lr()           # (the rate is a launch argument of this path: a schedule is evaluated on the host)
-        self.step_count += 1
-        if self.ema is not None:
-            _rn.check(L_.rn_ema_decay_eval(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(), _rn.f32(self.ema_dev),
-                                           _rn.stream()), 'rn_ema_decay_eval')
-        self._update(0, a.count, grad_scale, advance_counter, lr=lr, step=self.step_count)
-        import ops_f16
-        ops_f16.weights_changed()      # fp16-packed copies of the kernels (inference path) are stale now
-
-    def _step_clipped(self, grad_scale, advance_counter):
-        """The clipped update on a device arena: the norm is an INPUT of the update, so it takes a pass of its own over w and g --
-        into `_partial`, finalised into `norm_reg` -- and the update kernel forms clip / max(sqrt(norm_reg[0]), clip) from the
-        device scalar.  Rate and decay are read from the device like in the unclipped slices (begin_step); nothing here allocates,
-        synchronises or reads a device value, so the sequence is recorded into the one-graph step as it is launched eagerly.  The
-        one launch argument that changes from step to step is Adam's `step` WITHOUT a schedule (Trainer._whole_step_ok)."""
-        a, L_ = self.arena, _rn.lib()
-        self.begin_step()
-        self._pairs = int(L_.rn_optimizer_norm_pairs(a.count))
-        assert 2 * self._pairs <= self._partial.numel()
-        _rn.check(L_.rn_grad_norm_partial(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count, grad_scale,
-                                          self._partial.data_ptr(), _rn.stream()), 'rn_grad_norm_partial')
-        _rn.check(L_.rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),
-                  'rn_norm_reg_finalize')
-        self._update(0, a.count, grad_scale, advance_counter)
-        import ops_f16
-        ops_f16.weights_changed()
-
-    def _step_guarded(self, grad_scale, advance_counter):
-        """The update behind the guard (skip_nonfinite), clipped or not: norm pass, finalize, rn_finite_gate_eval, then the schedule's
-        and the average's one-thread kernels and the update, all three behind `gate_dev`.  begin_step's UNGATED one-thread kernels
-        do not run on this path: on a skipped step the words they advance must stay.  One stream, nothing allocated, no device
-        value read: the sequence is recorded into the one-graph step as it is launched eagerly, and no launch argument changes
-        from step to step (momentum's constant rate is the only host scalar; Adam and RMSProp read theirs from lr_dev)."""
-        a, L_ = self.arena, _rn.lib()
-        self.count_step()               # (the host counts an update per step; reconcile_skips takes the skipped ones out again)
-        assert self._partial is not None and (self.kind == 'momentum' or self.lr_dev is not None)
-        self._pairs = int(L_.rn_optimizer_norm_pairs(a.count))
-        assert 2 * self._pairs <= self._partial.numel()
-        _rn.check(L_.rn_grad_norm_partial(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count, grad_scale,
-                                          self._partial.data_ptr(), _rn.stream()), 'rn_grad_norm_partial')
-        _rn.check(L_.rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),
-                  'rn_norm_reg_finalize')
-        _rn.check(L_.rn_finite_gate_eval(_rn.f32(self.norm_reg), self.gate_dev.data_ptr(), self.skipped_dev.data_ptr(), _rn.stream()),
-                  'rn_finite_gate_eval')
-        if self.lr_dev is not None:
-            _rn.check(L_.rn_lr_schedule_eval_gated(self._sched_struct, self.step_dev.data_ptr(), _rn.f32(self.lr_dev), _rn.OPT[self.kind],
-                                                   self.gate_dev.data_ptr(), _rn.stream()), 'rn_lr_schedule_eval_gated')
-        if self.ema is not None:
-            _rn.check(L_.rn_ema_decay_eval_gated(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(),
-                                                 _rn.f32(self.ema_dev), self.gate_dev.data_ptr(), _rn.stream()), 'rn_ema_decay_eval_gated')
-        self._update(0, a.count, grad_scale, advance_counter, step=1)
-        import ops_f16
-        ops_f16.weights_changed()
+        """The sequence of the class docstring over the whole arena.  `advance_counter`: the device word the dropout masks hash;
+        bumped by the update kernel itself."""
+        self.begin_step(grad_scale)
+        self.step_slice(0, self.arena.count, grad_scale, advance_counter)
+        self.finish_step()
 
     def reconcile_skips(self):
         """(updates skipped in all, updates skipped in a row) from the device -- this SYNCHRONISES -- and step_count brought back to
@@ -416,64 +347,61 @@ class Optimizer(object):
             self.skipped_dev[1] = 0
             self._skips_seen = int(total)
 
-    # -- the update in slices of the arena (no clipping): Trainer.step updates the heads + FPN slice on a side stream while the
-    # backbone's backward pass still runs, the rest after it; every slice's launch leaves its share of (sum g'^2, regulariser)
-    def begin_step(self):
-        applying = self.count_step()
+    # -- the three pieces of the sequence.  Trainer-side callers drive them directly to update the arena in slices (RN_OPT_F_NORM
+    # only): the heads + FPN slice on a side stream while the backbone's backward pass still runs, the rest after it; every slice's
+    # launch leaves its share of (sum g'^2, regulariser)
+    def begin_step(self, grad_scale=1.0):
+        """count_step, the norm where it is formed ahead of the update (`grad_scale` is read only there), the control launch."""
+        a, L_ = self.arena, _rn.lib()
+        self._host_lr = self.current_lr()           # this update's rate where it is a launch argument: before the count moves
+        applying = self.count_step()                # (under the guard reconcile_skips takes the skipped ones out again)
         # (the update this micro-step's cycle ends in, 1-based: Adam's bias correction where the rate is a launch argument)
         self._update_no = self.step_count if applying else self.step_count + 1
         self._pairs = 0
-        assert self._partial is not None, "the fused norm path needs a device arena"
-        if self.acc is not None:
-            self._begin_accum_step()
-            return
-        if self.lr_dev is not None:
-            # this update's rate, on the main stream ahead of every slice; the kernel advances step_dev itself
-            _rn.check(_rn.lib().rn_lr_schedule_eval(self._sched_struct, self.step_dev.data_ptr(), _rn.f32(self.lr_dev),
-                                                    _rn.OPT[self.kind], _rn.stream()), 'rn_lr_schedule_eval')
-        if self.ema is not None:
-            # 1 - d(n) of this update, beside the rate; the kernel advances ema_updates_dev itself
-            _rn.check(_rn.lib().rn_ema_decay_eval(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(),
-                                                  _rn.f32(self.ema_dev), _rn.stream()), 'rn_ema_decay_eval')
-        if self.lr_dev is not None or self.ema is not None:
-            self._sched_event = torch.cuda.Event()       # one event behind both one-thread kernels
-            self._sched_event.record()
-
-    def _begin_accum_step(self):
-        """begin_step with accumulate_steps > 1: the phase first, then the schedule's and the average's kernels behind its gate (they
-        do nothing on a micro-step that only sums), and ONE event behind all three -- a slice on a side stream reads accum_dev too."""
-        L_ = _rn.lib()
-        _rn.check(L_.rn_accum_phase_eval(self.accumulate_steps, self.micro_dev.data_ptr(), self.accum_dev.data_ptr(), _rn.stream()),
-                  'rn_accum_phase_eval')
-        if self.lr_dev is not None:
-            _rn.check(L_.rn_lr_schedule_eval_gated(self._sched_struct, self.step_dev.data_ptr(), _rn.f32(self.lr_dev), _rn.OPT[self.kind],
-                                                   self.accum_dev.data_ptr(), _rn.stream()), 'rn_lr_schedule_eval_gated')
-        if self.ema is not None:
-            _rn.check(L_.rn_ema_decay_eval_gated(self.ema_decay, int(self.ema_warmup), self.ema_updates_dev.data_ptr(),
-                                                 _rn.f32(self.ema_dev), self.accum_dev.data_ptr(), _rn.stream()), 'rn_ema_decay_eval_gated')
-        self._sched_event = torch.cuda.Event()
-        self._sched_event.record()
+        if not self._fused:
+            # a CPU arena or RN_FUSED_OPT_NORM=0: the norm pass sizes its own workspace
+            ws = _rn.workspace(L_.rn_optimizer_workspace(a.count), a.weights.device)
+            _rn.check(L_.rn_grad_norm_l2reg(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count,
+                                            grad_scale, _rn.f32(self.norm_reg), ws.data_ptr(), ws.numel(), _rn.stream()),
+                      'rn_grad_norm_l2reg')
+        elif not self._features & _rn.OPT_F_NORM:
+            self._pairs = int(L_.rn_optimizer_norm_pairs(a.count))
+            assert 2 * self._pairs <= self._partial.numel()
+            _rn.check(L_.rn_grad_norm_partial(_rn.f32(a.weights), _rn.f32(a.grads), _rn.f32(a.wd_per_block), a.count, grad_scale,
+                                              self._partial.data_ptr(), _rn.stream()), 'rn_grad_norm_partial')
+            _rn.check(L_.rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),
+                      'rn_norm_reg_finalize')
+        if self._control is not None:
+            # on the main stream ahead of every slice; the kernel advances the words it reads itself
+            _rn.check(L_.rn_step_control_eval(ctypes.byref(self._control), _rn.stream()), 'rn_step_control_eval')
+            if self._features & _rn.OPT_F_NORM:
+                self._control_event = torch.cuda.Event()
+                self._control_event.record()
 
     def step_slice(self, lo, hi, grad_scale, advance_counter=None, stream=None):
-        a, L_ = self.arena, _rn.lib()
+        a = self.arena
         assert 0 <= lo < hi <= a.count and lo % OPT_BLOCK == 0 and hi % OPT_BLOCK == 0
-        assert self._features & _rn.OPT_F_NORM, "slices form the norm beside the update: not with clipping or the guard"
-        npairs = int(L_.rn_optimizer_norm_pairs(hi - lo))
-        assert 2 * (self._pairs + npairs) <= self._partial.numel()
-        part = self._partial[2 * self._pairs:]
-        self._pairs += npairs
-        if (self.lr_dev is not None or self.ema is not None or self.acc is not None) and stream is not None:
-            # a slice on another stream reads lr_dev / ema_dev / accum_dev too: behind the one-thread kernels, not the whole main stream
+        part = None
+        if self._features & _rn.OPT_F_NORM:
+            npairs = int(_rn.lib().rn_optimizer_norm_pairs(hi - lo))
+            assert 2 * (self._pairs + npairs) <= self._partial.numel()
+            part = self._partial[2 * self._pairs:]
+            self._pairs += npairs
+        else:
+            assert (lo, hi) == (0, a.count), "slices form the norm beside the update: not with clipping, the guard or a CPU arena"
+        if self._control_event is not None and stream is not None:
+            # a slice on another stream reads lr_dev / ema_dev / accum_dev too: behind the control launch, not the whole main stream
             other = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(getattr(stream, 'value', stream)))
-            other.wait_event(self._sched_event)
+            other.wait_event(self._control_event)
             stream = ctypes.c_void_p(other.cuda_stream)
         self._update(lo, hi, grad_scale, advance_counter, partial=part, stream=stream)
 
     def finish_step(self):
-        _rn.check(_rn.lib().rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),
-                  'rn_norm_reg_finalize')
+        if self._features & _rn.OPT_F_NORM:
+            _rn.check(_rn.lib().rn_norm_reg_finalize(self._partial.data_ptr(), self._pairs, _rn.f32(self.norm_reg), _rn.stream()),
+                      'rn_norm_reg_finalize')
         import ops_f16
-        ops_f16.weights_changed()
+        ops_f16.weights_changed()      # fp16-packed copies of the kernels (inference path) are stale now
 
     def current_lr(self):
         """The rate of the NEXT update, from the host's step count (no device synchronisation)."""
@@ -488,13 +416,13 @@ class Optimizer(object):
             self.ema_updates_dev.fill_(self.step_count)
 
     def set_accum_micro(self, n):
-        """Micro-steps taken so far (a restored checkpoint): the device word rn_accum_phase_eval reads and the host's phase."""
+        """Micro-steps taken so far (a restored checkpoint): the device word the control launch reads and the host's phase."""
         if self.acc is not None:
             self.micro_dev.fill_(int(n))
             self._phase = int(n) % self.accumulate_steps
 
     def ema_decay_value(self, n):
-        """d(n), the decay of the update that follows n applied ones, in float64: the host's copy of what rn_ema_decay_eval forms."""
+        """d(n), the decay of the update that follows n applied ones, in float64: the host's copy of what the control launch forms."""
         if self.ema_decay is None:
             raise ValueError("this optimizer keeps no moving average (ema_decay=None)")
         n = int(n)
@@ -613,6 +541,14 @@ class GradientAllReduce(object):
         return self.wait()
 
 
+# The captured graphs of one input shape (Trainer._graphs; callers outside this file read the first six by position).
+#   whole = False (_capture): `first` is segment A and `parts` / `ranges` one graph and one arena slice per part of segment B;
+#     deferred_in_part0: the tower weight gradients are forked and joined inside parts[0], the subnets' slice is complete behind it
+#   whole = True (_capture_whole): `first` is the whole step; `ranges` the parts' slices, kept for reporting; `schedule` the
+#     slices in the order the recorded step reduces them
+StepGraphs = collections.namedtuple('StepGraphs', 'first parts ranges out static whole deferred_in_part0 schedule')
+
+
 class Trainer(object):
     """One data-parallel replica.  `step(features)` = forward + loss + backward + gradient
     all-reduce + optimizer.
@@ -653,11 +589,8 @@ class Trainer(object):
         # skip_nonfinite: the update of a step whose global gradient norm is not finite does not happen (Optimizer docstring).  Gate
         # and counters live on the device: the step stays ONE graph, the guard is part of its cache key, and Adam / RMSProp at a
         # constant rate read it from the device then, so they qualify for the one-graph step as with an lr_schedule
-        ema_kw = {} if ema_decay is None else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}
-        if skip_nonfinite:
-            ema_kw['skip_nonfinite'] = True
-        self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule,
-                             accumulate_steps=accumulate_steps, **ema_kw)
+        self.opt = Optimizer(self.arena, optimizer, learning_rate, grad_clip_norm, schedule=lr_schedule, ema_decay=ema_decay,
+                             ema_warmup=ema_warmup, accumulate_steps=accumulate_steps, skip_nonfinite=skip_nonfinite)
         # train_metrics: the reference's streaming training metrics (build_metrics, train.py:137-161: loss means, class_iou,
         # regr_iou) as running totals on the device (metrics.TrainMetrics).  One pass behind the loss over the tensors it has just
         # read and one block behind the update: two more nodes of the SAME graph(s), or two eager launches; the host reads them only
@@ -998,17 +931,22 @@ class Trainer(object):
             ops.advance_dropout_counter(self.drop_counter)
         return out
 
-    def _run_step(self, features=None, timed=False):
-        """The device work of ONE step in issue order -- the same sequence whether it is launched eagerly or recorded into one
-        graph, with one rank or many (MirroredStrategy's per-tower step + cross-tower sum, train.py:111-134, 261-267):
+    def _run_step(self, features=None, timed=False, replay=None):
+        """The device work of ONE step in issue order -- the same sequence whether it is launched eagerly, recorded into one graph
+        or replayed from one graph per part, with one rank or many (MirroredStrategy's per-tower step + cross-tower sum,
+        train.py:111-134, 261-267):
 
             segment A (assignment, forward, loss, backward of the heads and the FPN; tower weight gradients recorded, not run)
             all-reduce  [cut_offset, heads_offset)      the FPN's slice             } under segment B
-            fork: deferred tower weight gradients  ->  all-reduce [heads_offset, count) behind them, on their stream
+            fork: deferred tower weight gradients  ->  all-reduce [heads_offset, count) behind them
             for every part j of the backbone's backward pass, last stage first:  part j  ->  all-reduce of its slice
             join, wait for the collectives, optimizer update (1 / world folded in; bumps the dropout counter); with
             grad_clip_norm the norm pass runs here too, behind the wait: the norm of the REDUCED gradient times 1 / world
 
+        `replay` (the StepGraphs of _capture): segment A and the parts are replays of their graphs, not launches.  A forked stream
+        must be joined inside the graph that forked it, so part 0's graph holds the deferred products whole and the subnets' slice
+        is reduced right behind that replay; launched, it is reduced on the products' own stream, by segment_b's callback.
+        `schedule` -- the order the slices' collectives are issued in -- is the same either way.
         Without deferred products the first collective covers [cut_offset, count).  With one rank launch() / wait() do nothing."""
         ar = self.allreduce
         del self.schedule[:]
@@ -1018,17 +956,32 @@ class Trainer(object):
                 self.schedule.append((lo, hi))
                 ar.launch(lo, hi)
 
-        class_loss, regr_loss = self.segment_a(features)
-        deferred = bool(self._deferred_wgrads) and bool(self._parts)
+        if replay is None:
+            class_loss, regr_loss = self.segment_a(features)
+            n = self.num_parts()
+            deferred = bool(self._deferred_wgrads) and n > 0
+
+            def run_part(j, after):
+                return self.segment_b(j, join_wgrads=False, after_wgrads=after)
+        else:
+            replay.first.replay()
+            class_loss, regr_loss = replay.out
+            n, deferred = len(replay.parts), replay.deferred_in_part0
+
+            def run_part(j, after):
+                replay.parts[j].replay()
+                if j == 0 and after is not None:
+                    after()
+                return replay.ranges[j]
+
         top = self.heads_offset if (deferred and ar.active) else self.arena.count
         reduce(self.cut_offset, top)                       # heads + FPN (or the FPN alone): under the backbone's backward pass
         after = (lambda: reduce(top, self.arena.count)) if top < self.arena.count else None
-        n = self.num_parts()
         for j in range(n if n else (1 if self.cut_offset else 0)):
-            rng = self.segment_b(j, join_wgrads=False, after_wgrads=after) if n else None
+            rng = run_part(j, after) if n else None
             reduce(*(rng or (0, self.cut_offset)))         # this part's slice: under the parts that follow
         self._parts = []
-        if deferred:
+        if deferred and replay is None:
             self._join_wgrads()
         if timed and self.timing is not None and self.device.type == 'cuda':
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1089,8 +1042,7 @@ class Trainer(object):
                 ranges.append(self.segment_b(j))   # (deferred weight gradients, if any, are forked AND joined inside the first part)
             gbs.append(gb)
         self._parts = []
-        # (index 6: were tower weight gradients deferred into the first part's graph?  Then the subnets' slice is complete after it)
-        self._graphs = (ga, gbs, ranges, self._graph_out, self._static, False, had_deferred)
+        self._graphs = StepGraphs(ga, gbs, ranges, self._graph_out, self._static, False, had_deferred, None)
 
     def _whole_step_ok(self):
         ar = self.allreduce
@@ -1109,7 +1061,7 @@ class Trainer(object):
         self.opt.step_count, self.opt._phase = count, phase      # (recorded, not run: replays count their own steps)
         ranges = [r for r in self.schedule if r[1] <= self.cut_offset]
         # (the parts' arena ranges are kept for reporting; no graph per part)
-        self._graphs = (g, [], ranges, self._graph_out, self._static, True, list(self.schedule))
+        self._graphs = StepGraphs(g, [], ranges, self._graph_out, self._static, True, False, list(self.schedule))
 
     def step(self, features=None):
         # a feed (dataset.DeviceFeed: input_fn with stage / consumed) puts a NEW sample into its static device buffers before
@@ -1152,43 +1104,20 @@ class Trainer(object):
             else:
                 self._graph_cache.move_to_end(key)
                 self._graphs = cached
-                self._graph_out, self._static = cached[3], cached[4]
+                self._graph_out, self._static = cached.out, cached.static
                 if features is not None:
                     _copy_tree(self._static, features)
-            self._graphs[0].replay()
-            class_loss, regr_loss = self._graph_out
-            if self._graphs[5]:
+            g = self._graphs
+            if g.whole:
                 # the whole step was that one replay: what is left is the update's host-side bookkeeping
-                self.schedule[:] = self._graphs[6]
+                g.first.replay()
+                class_loss, regr_loss = g.out
+                self.schedule[:] = g.schedule
                 self.opt.count_step()               # (updates, not replays: every accumulate_steps-th replay applied one)
                 import ops_f16
                 ops_f16.weights_changed()
             else:
-                del self.schedule[:]
-                ar = self.allreduce
-
-                def reduce(lo, hi):
-                    if hi > lo:
-                        self.schedule.append((lo, hi))
-                        ar.launch(lo, hi)
-                deferred = bool(self._graphs[6]) and ar.active
-                top = self.heads_offset if deferred else self.arena.count
-                reduce(self.cut_offset, top)                          # heads + FPN (or the FPN alone): under the backbone's backward pass
-                for j, (gb, (lo, hi)) in enumerate(zip(self._graphs[1], self._graphs[2])):
-                    gb.replay()
-                    if j == 0 and deferred:
-                        reduce(top, self.arena.count)                 # the subnets' slice: its deferred products ran (and joined) inside part 0
-                    reduce(lo, hi)                                    # this part's slice: under the parts that follow
-                if self.timing is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    grad_scale = ar.wait()
-                    e1.record()
-                    self.timing.setdefault('exposed_events', []).append((e0, e1))
-                else:
-                    grad_scale = ar.wait()
-                self.opt.step(grad_scale, self.drop_counter)
-                self._fold_metrics(class_loss, regr_loss)
+                class_loss, regr_loss = self._run_step(timed=True, replay=g)
         else:
             class_loss, regr_loss = self._run_step(features, timed=True)
         if feed is not None:

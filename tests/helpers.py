@@ -98,3 +98,11 @@ def dropout_sites(net, rate, counter=0):
                 name = "backbone." + name if name else name
             seeds[name] = m.seed
     return dropout_ref.Sites(seeds, rate, counter)
+
+
+def step_control(stream=None, **fields):
+    """rn_step_control_eval on a descriptor with exactly the given fields set (the rest stay 0 / null); returns its status."""
+    import ctypes
+    import _rn
+    c = _rn.StepControl(**fields)
+    return _rn.lib().rn_step_control_eval(ctypes.byref(c), stream)

@@ -13,7 +13,7 @@ import step_tail_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("momentum", "rmsprop", "adam")
-NEW_SYMBOLS = ("rn_accum_phase_eval", "rn_lr_schedule_eval_gated", "rn_ema_decay_eval_gated", "rn_optimizer_update")
+NEW_SYMBOLS = ("rn_step_control_eval", "rn_optimizer_update")
 
 
 def _same(a, b):
@@ -98,6 +98,7 @@ def test_entries_refuse_bad_arguments_without_a_launch():
     pointers that are never dereferenced."""
     import _rn
     import train
+    from helpers import step_control
     L = _rn.lib()
     buf = torch.zeros(2048 + 4, dtype=torch.float32)
     base = buf.data_ptr() + (-buf.data_ptr()) % 16                   # a 16-byte aligned host address
@@ -105,16 +106,21 @@ def test_entries_refuse_bad_arguments_without_a_launch():
     pair = torch.zeros(2, dtype=torch.int32).data_ptr()
     two = torch.zeros(2, dtype=torch.float32).data_ptr()
     part = torch.zeros(8, dtype=torch.float64).data_ptr()
-    for A in (0, -3):
-        assert L.rn_accum_phase_eval(A, word, pair, None) != 0
-    assert L.rn_accum_phase_eval(2, None, pair, None) != 0 and L.rn_accum_phase_eval(2, word, None, None) != 0
     sched = train.LRSchedule("constant", 0.1).struct()
-    assert L.rn_lr_schedule_eval_gated(sched, word, two, 0, None, None) != 0
-    assert L.rn_lr_schedule_eval_gated(sched, None, two, 0, pair, None) != 0
-    assert L.rn_lr_schedule_eval_gated(sched, word, two, 7, pair, None) != 0         # (the ungated entry's checks come along)
-    assert L.rn_ema_decay_eval_gated(0.5, 1, word, two, None, None) != 0
-    assert L.rn_ema_decay_eval_gated(0.5, 1, word, None, pair, None) != 0
-    assert L.rn_ema_decay_eval_gated(1.0, 1, word, two, pair, None) != 0
+
+    def ctl(A=2, micro_dev=word, accum_dev=pair, features=_rn.CTL_F_ACCUM, **fields):
+        return step_control(features=features, accumulate_steps=A, micro_dev=micro_dev, accum_dev=accum_dev, **fields)
+    for A in (0, -3):
+        assert ctl(A=A) != 0
+    assert ctl(micro_dev=None) != 0 and ctl(accum_dev=None) != 0
+    lr = dict(features=_rn.CTL_F_ACCUM | _rn.CTL_F_LR, schedule=sched, step_dev=word, lr_dev=two)
+    assert ctl(**dict(lr, accum_dev=None)) != 0                                      # the gate's word
+    assert ctl(**dict(lr, step_dev=None)) != 0
+    assert ctl(optimizer_kind=7, **lr) != 0                                          # (the ungated checks come along)
+    ema = dict(features=_rn.CTL_F_ACCUM | _rn.CTL_F_EMA, ema_decay=0.5, ema_warmup=1, ema_updates_dev=word, ema_dev=two)
+    assert ctl(**dict(ema, accum_dev=None)) != 0
+    assert ctl(**dict(ema, ema_dev=None)) != 0
+    assert ctl(**dict(ema, ema_decay=1.0)) != 0
 
     def step(acc=base, accum_dev=pair, partial=part, count=1024, inv=0.5, ema=None, ema_dev=None, state2=None, kind=0):
         f = _rn.OPT_F_NORM | _rn.OPT_F_ACCUM | (_rn.OPT_F_EMA if None not in (ema, ema_dev) else 0)

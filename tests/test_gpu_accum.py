@@ -1,4 +1,4 @@
-"""Gradient accumulation on the MI355X (-m gpu): rn_accum_phase_eval and the gated one-thread kernels, the accumulating update
+"""Gradient accumulation on the MI355X (-m gpu): rn_step_control_eval's phase and what runs behind its gate, the accumulating update
 kernel against the float64 reference (accum_ref.py) and, bit for bit, against a plain update on exact means, an accumulating
 trainer's ONE captured graph against eager launches, the reference and a checkpoint taken in the middle of a cycle, and the command
 line."""
@@ -13,7 +13,7 @@ import accum_ref as ref
 import ema_ref
 import lr_schedule_ref
 import step_tail_ref
-from helpers import assert_close, elementwise_rel_err
+from helpers import assert_close, elementwise_rel_err, step_control
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4          # (test_gpu_ema.TOL: max-norm and element-wise, through assert_close)
@@ -43,11 +43,11 @@ def _same_bits(a, b):
 
 # ------------------------------------------------------------------------------------------------ the one-thread kernels
 def test_phase_kernel_and_gates(dev):
-    """A = 3, 7 launches of the three one-thread kernels: accum_dev = [m % 3, m % 3 == 2] and the micro-step word exact after each;
+    """A = 3, 7 launches of the control kernel (ACCUM | LR | EMA): accum_dev = [m % 3, m % 3 == 2] and the micro-step word exact after each;
     the gated schedule (Adam: with the bias correction) and average kernels act on launches 3 and 6 only -- there within 1 ulp of
     the float64 formulas, words advanced -- and leave lr_dev / ema_dev bit-unchanged, words untouched, on the others."""
     import _rn, train
-    L, A = _rn.lib(), 3
+    A = 3
     sched = train.LRSchedule("cosine", 1e-2, warmup_steps=1, total_steps=5, final_factor=0.05)
     kw = dict(kind="cosine", base=1e-2, warmup_steps=1, total_steps=5, final_factor=0.05)
     d = sched.struct()
@@ -58,12 +58,11 @@ def test_phase_kernel_and_gates(dev):
     lr_dev = torch.tensor([7.0, 9.0], dtype=torch.float32, device=dev)            # (sentinels: a closed gate leaves them)
     ema_dev = torch.tensor([5.0, 3.0], dtype=torch.float32, device=dev)
     prev_lr, prev_ema, u = lr_dev.cpu().numpy(), ema_dev.cpu().numpy(), 0
+    lr_ema = dict(optimizer_kind=_rn.OPT["adam"], schedule=d, step_dev=step_dev.data_ptr(), lr_dev=_rn.f32(lr_dev),
+                  ema_decay=0.22, ema_warmup=1, ema_updates_dev=upd_dev.data_ptr(), ema_dev=_rn.f32(ema_dev))
     for m in range(7):
-        _rn.check(L.rn_accum_phase_eval(A, micro.data_ptr(), pair.data_ptr(), _rn.stream()), "rn_accum_phase_eval")
-        _rn.check(L.rn_lr_schedule_eval_gated(d, step_dev.data_ptr(), _rn.f32(lr_dev), _rn.OPT["adam"], pair.data_ptr(), _rn.stream()),
-                  "rn_lr_schedule_eval_gated")
-        _rn.check(L.rn_ema_decay_eval_gated(0.22, 1, upd_dev.data_ptr(), _rn.f32(ema_dev), pair.data_ptr(), _rn.stream()),
-                  "rn_ema_decay_eval_gated")
+        _rn.check(step_control(_rn.stream(), features=_rn.CTL_F_ACCUM | _rn.CTL_F_LR | _rn.CTL_F_EMA, accumulate_steps=A,
+                               micro_dev=micro.data_ptr(), accum_dev=pair.data_ptr(), **lr_ema), "rn_step_control_eval")
         assert pair.cpu().tolist() == [m % A, int(m % A == A - 1)] and int(micro.item()) == m + 1
         got_lr, got_ema = lr_dev.cpu().numpy(), ema_dev.cpu().numpy()
         if m % A == A - 1:
@@ -78,9 +77,8 @@ def test_phase_kernel_and_gates(dev):
         assert int(step_dev.item()) == u == int(upd_dev.item())
         prev_lr, prev_ema = got_lr, got_ema
     assert u == 2 and prev_lr[0] != 7.0 and prev_ema[0] != 5.0
-    # the ungated entries are as they were: they act on every launch
-    _rn.check(L.rn_lr_schedule_eval(d, step_dev.data_ptr(), _rn.f32(lr_dev), _rn.OPT["adam"], _rn.stream()), "rn_lr_schedule_eval")
-    _rn.check(L.rn_ema_decay_eval(0.22, 1, upd_dev.data_ptr(), _rn.f32(ema_dev), _rn.stream()), "rn_ema_decay_eval")
+    # LR | EMA without ACCUM / GUARD has no gate: it acts on every launch (micro-step 7 is phase 1: the gated launch would not)
+    _rn.check(step_control(_rn.stream(), features=_rn.CTL_F_LR | _rn.CTL_F_EMA, **lr_ema), "rn_step_control_eval")
     assert int(step_dev.item()) == 3 == int(upd_dev.item())
     assert lr_schedule_ref.ulp_distance(lr_dev[0].item(), sched.value(2)) <= 1
 

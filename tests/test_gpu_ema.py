@@ -1,4 +1,4 @@
-"""The moving average of the weights on the MI355X (-m gpu): rn_ema_decay_eval against the float64 formula, the average the
+"""The moving average of the weights on the MI355X (-m gpu): rn_step_control_eval (EMA) against the float64 formula, the average the
 update kernel keeps against the float64 reference (ema_ref.py) on the synthetic arenas of test_gpu_step_tail.py, an EMA trainer's
 ONE captured graph against eager launches and across a checkpoint, Trainer.ema_weights(), and the command line."""
 import collections
@@ -13,7 +13,7 @@ import torch
 import ema_ref as ref
 import lr_schedule_ref
 import step_tail_ref
-from helpers import assert_close, elementwise_rel_err
+from helpers import assert_close, elementwise_rel_err, step_control
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -38,6 +38,12 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def _decay_eval(decay, warmup, word, ema_dev):
+    """The control launch with the average's part alone: word and ema_dev are device pointers (or None)."""
+    import _rn
+    return step_control(_rn.stream(), features=_rn.CTL_F_EMA, ema_decay=decay, ema_warmup=int(warmup), ema_updates_dev=word, ema_dev=ema_dev)
+
+
 # ------------------------------------------------------------------------------------------------ the one-thread kernel
 @pytest.mark.parametrize("setting", SETTINGS)
 def test_device_decay_values(dev, setting):
@@ -47,7 +53,7 @@ def test_device_decay_values(dev, setting):
     word = torch.zeros(1, dtype=torch.int64, device=dev)
     ema_dev = torch.zeros(2, dtype=torch.float32, device=dev)
     for n in range(12):
-        _rn.check(_rn.lib().rn_ema_decay_eval(s.decay, int(s.warmup), word.data_ptr(), _rn.f32(ema_dev), _rn.stream()), "rn_ema_decay_eval")
+        _rn.check(_decay_eval(s.decay, s.warmup, word.data_ptr(), _rn.f32(ema_dev)), "rn_step_control_eval")
         got = ema_dev.cpu().numpy()
         d, om = ref.decay_pair(n, s.decay, s.warmup)
         assert lr_schedule_ref.ulp_distance(got[0], d) <= 1, (setting, n, got[0], d)
@@ -56,7 +62,7 @@ def test_device_decay_values(dev, setting):
     assert int(word.item()) == 12
     # a late update: D binds under warm-up, and 1 - D is rounded from float64 (not 1 - float32(D))
     word.fill_(10 ** 6)
-    _rn.check(_rn.lib().rn_ema_decay_eval(s.decay, int(s.warmup), word.data_ptr(), _rn.f32(ema_dev), _rn.stream()), "rn_ema_decay_eval")
+    _rn.check(_decay_eval(s.decay, s.warmup, word.data_ptr(), _rn.f32(ema_dev)), "rn_step_control_eval")
     d, om = ref.decay_pair(10 ** 6, s.decay, s.warmup)
     got = ema_dev.cpu().numpy()
     assert lr_schedule_ref.ulp_distance(got[0], d) <= 1 and lr_schedule_ref.ulp_distance(got[1], om) <= 1
@@ -69,9 +75,9 @@ def test_entries_refuse_bad_arguments(dev):
     word = torch.zeros(1, dtype=torch.int64, device=dev)
     ema_dev = torch.zeros(2, dtype=torch.float32, device=dev)
     for bad in (0.0, 1.0, -0.1, 1.5, float("nan")):
-        assert L.rn_ema_decay_eval(bad, 1, word.data_ptr(), _rn.f32(ema_dev), _rn.stream()) != 0
-    assert L.rn_ema_decay_eval(0.5, 1, None, _rn.f32(ema_dev), _rn.stream()) != 0
-    assert L.rn_ema_decay_eval(0.5, 1, word.data_ptr(), None, _rn.stream()) != 0
+        assert _decay_eval(bad, 1, word.data_ptr(), _rn.f32(ema_dev)) != 0
+    assert _decay_eval(0.5, 1, None, _rn.f32(ema_dev)) != 0
+    assert _decay_eval(0.5, 1, word.data_ptr(), None) != 0
     torch.cuda.synchronize()
     assert int(word.item()) == 0 and not ema_dev.cpu().numpy().any()          # nothing was launched
     w = torch.zeros(1024, dtype=torch.float32, device=dev)

@@ -1,7 +1,7 @@
-"""The guard against non-finite gradients (skip_nonfinite) on the MI355X (-m gpu): rn_finite_gate_eval and the gated update
+"""The guard against non-finite gradients (skip_nonfinite) on the MI355X (-m gpu): rn_step_control_eval's gate and the gated update
 against the float64 reference (guard_ref.py), a skipped update bit for bit, guard on against guard off on finite gradients,
-Optimizer.step() captured and replayed, the two entries called directly, and a guarded trainer's ONE captured graph over a poisoned
-step, against eager launches, a checkpoint and the command line.
+Optimizer.step() captured and replayed, the two entries called directly, the one launch sequence of every configuration, and a
+guarded trainer's ONE captured graph over a poisoned step, against eager launches, a checkpoint and the command line.
 
 TOL = 1e-4, element-wise, is test_gpu_clip_graph.py's bar for this arithmetic; everything that is not a comparison with float64
 is bit equality."""
@@ -17,7 +17,7 @@ import ema_ref
 import guard_ref as ref
 import lr_schedule_ref
 import step_tail_ref
-from helpers import assert_close, elementwise_rel_err
+from helpers import assert_close, elementwise_rel_err, step_control
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -61,7 +61,7 @@ def _snapshot(arena, opt, counter):
                _np(opt.ema_updates_dev), _np(opt.ema_dev), _np(opt.gate_dev), _np(opt.skipped_dev), int(counter.item()))
 
 
-def _make(dev, inp, kind, clip=None, scheduled=False, setting=None, guard=True, schedule=None):
+def _make(dev, inp, kind, clip=None, scheduled=False, setting=None, guard=True, schedule=None, accumulate_steps=1):
     """test_gpu_clip_graph._make with the guard's keyword: a synthetic module laid out as `inp` and its optimizer."""
     import train
     assert train.FUSED_OPT_NORM
@@ -83,7 +83,7 @@ def _make(dev, inp, kind, clip=None, scheduled=False, setting=None, guard=True, 
         kw.update(schedule=train.LRSchedule(base_lr=inp.lr, **ref.SCHEDULE))
     if guard:
         kw.update(skip_nonfinite=True)
-    return mod, arena, train.Optimizer(arena, kind, inp.lr, grad_clip_norm=clip, **kw)
+    return mod, arena, train.Optimizer(arena, kind, inp.lr, grad_clip_norm=clip, accumulate_steps=accumulate_steps, **kw)
 
 
 def _load_grad(arena, inp, g, dev):
@@ -261,7 +261,7 @@ def test_step_captured_and_replayed_equals_eager(dev):
 
 
 def test_entries_called_directly(dev):
-    """rn_finite_gate_eval on norm_sq 1, 0, inf, nan (and -inf, FLT_MAX): gates 1, 1, 0, 0 (0, 1) and the counters that go with
+    """rn_step_control_eval (GUARD) on norm_sq 1, 0, inf, nan (and -inf, FLT_MAX): gates 1, 1, 0, 0 (0, 1) and the counters that go with
     them; the gated update with the gate closed touches nothing but the counter; bad arguments come back negative."""
     import _rn
     L = _rn.lib()
@@ -270,9 +270,12 @@ def test_entries_called_directly(dev):
     skipped = torch.zeros(2, dtype=torch.int64, device=dev)
     fmax = float(np.finfo(np.float32).max)
     want_total = want_row = 0
+
+    def finite_gate(norm_sq, gate_dev, skipped_dev, stream):
+        return step_control(stream, features=_rn.CTL_F_GUARD, norm_sq=norm_sq, gate_dev=gate_dev, skipped_dev=skipped_dev)
     for v, g in ((1.0, 1), (0.0, 1), (float("inf"), 0), (float("nan"), 0), (float("nan"), 0), (fmax, 1), (float("-inf"), 0), (1.0, 1)):
         norm[0] = v
-        _rn.check(L.rn_finite_gate_eval(_rn.f32(norm), gate.data_ptr(), skipped.data_ptr(), _rn.stream()), "rn_finite_gate_eval")
+        _rn.check(finite_gate(_rn.f32(norm), gate.data_ptr(), skipped.data_ptr(), _rn.stream()), "rn_step_control_eval")
         want_total, want_row = want_total + (1 - g), (0 if g else want_row + 1)
         assert gate.tolist() == [0, g] and skipped.tolist() == [want_total, want_row], v
     assert want_total == 4
@@ -303,8 +306,8 @@ def test_entries_called_directly(dev):
     assert torch.equal(s1, grad) and torch.equal(w, w0 - 0.5 * grad) and counter.item() == 6
     # refusals (no launch)
     q = ctypes.c_void_p(norm.data_ptr())
-    assert L.rn_finite_gate_eval(None, q, q, None) < 0 and L.rn_finite_gate_eval(q, None, q, None) < 0 and L.rn_finite_gate_eval(q, q, None, None) < 0
-    assert L.rn_finite_gate_eval(q, ctypes.c_void_p(norm.data_ptr() + 2), q, None) < 0
+    assert finite_gate(None, q, q, None) < 0 and finite_gate(q, None, q, None) < 0 and finite_gate(q, q, None, None) < 0
+    assert finite_gate(q, ctypes.c_void_p(norm.data_ptr() + 2), q, None) < 0
     args = [0, _rn.f32(w), _rn.f32(grad), _rn.f32(s1), None, _rn.f32(wd), n, 0.5, None, 1.0, 0.0, None, 1, None, 0, None, None]
     assert gated(*(args + [None, None])) < 0
     assert gated(*(args[:10] + [-1.0] + args[11:] + [gate.data_ptr(), None])) < 0
@@ -313,6 +316,69 @@ def test_entries_called_directly(dev):
     assert gated(*([2] + args[1:] + [gate.data_ptr(), None])) < 0                         # Adam without state2
     torch.cuda.synchronize()
     assert torch.equal(w, w0 - 0.5 * grad)
+
+
+# ---------------------------------------------------------------------------------------------- the one sequence
+class _RecordingLib(object):
+    """_rn.lib() with the name of every rn_* entry called appended to `calls`; the call itself goes through."""
+
+    def __init__(self, lib, calls):
+        self._lib, self._calls = lib, calls
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("rn_"):
+            return fn
+
+        def call(*args):
+            self._calls.append(name)
+            return fn(*args)
+        return call
+
+
+NORM_AHEAD = ["rn_grad_norm_partial", "rn_norm_reg_finalize"]
+CONTROL, UPDATE, FINALIZE = "rn_step_control_eval", "rn_optimizer_update", "rn_norm_reg_finalize"
+SEQUENCES = {
+    # name: (keywords of _make, steps, the launches of ONE step in order)
+    "plain": (dict(guard=False), 1, [UPDATE, FINALIZE]),
+    "schedule": (dict(guard=False, scheduled=True), 1, [CONTROL, UPDATE, FINALIZE]),
+    "ema": (dict(guard=False, setting=SETTING), 1, [CONTROL, UPDATE, FINALIZE]),
+    "schedule+ema": (dict(guard=False, scheduled=True, setting=SETTING), 1, [CONTROL, UPDATE, FINALIZE]),
+    "clip": (dict(guard=False, clip=ref.CLIP_BINDS), 1, NORM_AHEAD + [UPDATE]),
+    "clip+schedule": (dict(guard=False, clip=ref.CLIP_BINDS, scheduled=True), 1, NORM_AHEAD + [CONTROL, UPDATE]),
+    "accum": (dict(guard=False, accumulate_steps=2), 2, [CONTROL, UPDATE, FINALIZE]),
+    "guard": (dict(guard=True), 1, NORM_AHEAD + [CONTROL, UPDATE]),
+    "guard+clip+schedule+ema": (dict(guard=True, clip=ref.CLIP_BINDS, scheduled=True, setting=SETTING), 1, NORM_AHEAD + [CONTROL, UPDATE]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SEQUENCES))
+def test_every_configuration_takes_the_one_sequence(dev, name, monkeypatch):
+    """Optimizer.step() on the small arena with every entry of librn_hip.so it calls recorded: norm ahead (clip, guard) ->
+    control (one launch; none for plain momentum at a constant rate) -> update -> finalize (where the norm is formed beside the
+    update), the same for every micro-step of an accumulation cycle.  Size queries launch nothing and are left out."""
+    import _rn
+    kw, steps, want = SEQUENCES[name]
+    inp = ref.guard_case()
+    _, arena, opt = _make(dev, inp, "momentum", **kw)
+    assert (opt._control is None) == (CONTROL not in want)
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    w_before = arena.weights.clone()
+    calls, lib = [], _rn.lib()
+    monkeypatch.setattr(_rn, "lib", lambda: _RecordingLib(lib, calls))
+    for i in range(steps):
+        _load_grad(arena, inp, inp.grads[i], dev)
+        del calls[:]
+        opt.step(grad_scale=inp.grad_scale, advance_counter=counter)
+        got = [c for c in calls if c not in ("rn_optimizer_norm_pairs", "rn_last_error")]
+        assert got == want, (name, i, calls)
+        assert got.count(CONTROL) <= 1 and got.count(UPDATE) == 1
+        if CONTROL in got and NORM_AHEAD[0] in got:
+            assert got.index(NORM_AHEAD[0]) < got.index(FINALIZE) < got.index(CONTROL) < got.index(UPDATE)
+    torch.cuda.synchronize()
+    assert opt.step_count == 1 and not torch.equal(arena.weights, w_before)
+    if opt.skipped_dev is not None:
+        assert opt.skipped_dev.tolist() == [0, 0] and opt.gate_dev.tolist() == [0, 1]
 
 
 # ---------------------------------------------------------------------------------------------- trainer

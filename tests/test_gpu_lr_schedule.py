@@ -1,4 +1,4 @@
-"""Learning-rate schedules on the MI355X (-m gpu): rn_lr_schedule_eval against train.LRSchedule.value, the device-rate update
+"""Learning-rate schedules on the MI355X (-m gpu): rn_step_control_eval (LR) against train.LRSchedule.value, the device-rate update
 against the CPU oracle, and a scheduled trainer's ONE captured graph against eager launches, against a constant-rate trainer fed the
 same rates by hand, and across a checkpoint."""
 import numpy as np
@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import lr_schedule_ref as ref
-from helpers import assert_close
+from helpers import assert_close, step_control
 from oracle import train_ref
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +39,8 @@ def test_device_schedule_values(dev, name, kind):
     lr_dev = torch.zeros(2, dtype=torch.float32, device=dev)
     d = sched.struct()
     for s in range(12):
-        _rn.check(_rn.lib().rn_lr_schedule_eval(d, step_dev.data_ptr(), _rn.f32(lr_dev), _rn.OPT[kind], _rn.stream()), "rn_lr_schedule_eval")
+        _rn.check(step_control(_rn.stream(), features=_rn.CTL_F_LR, optimizer_kind=_rn.OPT[kind], schedule=d, step_dev=step_dev.data_ptr(),
+                               lr_dev=_rn.f32(lr_dev)), "rn_step_control_eval")
         got = lr_dev.cpu().numpy()
         want = sched.value(s)
         assert ref.ulp_distance(got[0], want) <= 1, (name, kind, s, got[0], want)

@@ -15,7 +15,7 @@ import step_tail_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("momentum", "rmsprop", "adam")
-NEW_SYMBOLS = ("rn_finite_gate_eval", "rn_optimizer_update")
+NEW_SYMBOLS = ("rn_step_control_eval", "rn_optimizer_update")
 FLT_MAX = float(np.finfo(np.float32).max)
 
 
@@ -163,12 +163,7 @@ def test_the_guard_is_part_of_the_graph_key_and_adds_no_condition():
     assert "skip_nonfinite" in inspect.getsource(train.Trainer.step)
     src = inspect.getsource(train.Trainer._whole_step_ok)
     assert "skip" not in src and "gate" not in src and "lr_dev is not None" in src
-    # the ungated one-thread kernels of begin_step are not launched on the guarded path
-    guarded = inspect.getsource(train.Optimizer._step_guarded)
-    assert "begin_step" not in guarded.replace("begin_step's", "") and "rn_lr_schedule_eval(" not in guarded and "rn_ema_decay_eval(" not in guarded
-    order = [guarded.index(s) for s in ("L_.rn_grad_norm_partial(", "L_.rn_norm_reg_finalize(", "L_.rn_finite_gate_eval(",
-                                        "L_.rn_lr_schedule_eval_gated(", "L_.rn_ema_decay_eval_gated(", "self._update(0, a.count, grad_scale, advance_counter, step=1)")]
-    assert order == sorted(order)
+    # (the order of the guarded step's launches: tests/test_gpu_guard.py::test_every_configuration_takes_the_one_sequence)
 
 
 def test_new_symbols_are_exported_and_declared():
@@ -186,16 +181,31 @@ def test_entries_refuse_bad_arguments_without_a_launch():
     """Every call below is refused by the entry's own checks with RN_EINVAL (-1) and a message, ahead of any launch: fake non-null
     pointers that are never dereferenced."""
     import _rn
+    import train
+    from helpers import step_control
     L = _rn.lib()
     q, odd2, odd4 = ctypes.c_void_p(4096), ctypes.c_void_p(4096 + 2), ctypes.c_void_p(4096 + 4)
 
-    def gate(norm_sq=q, gate_dev=q, skipped=q):
-        return L.rn_finite_gate_eval(norm_sq, gate_dev, skipped, None)
-    assert gate(norm_sq=None) == -1 and b"finite_gate_eval" in L.rn_last_error()
+    def gate(norm_sq=q, gate_dev=q, skipped=q, features=_rn.CTL_F_GUARD, **fields):
+        return step_control(features=features, norm_sq=norm_sq, gate_dev=gate_dev, skipped_dev=skipped, **fields)
+    assert gate(norm_sq=None) == -1 and b"step_control" in L.rn_last_error() and b"GUARD" in L.rn_last_error()
     assert gate(gate_dev=None) == -1 and gate(skipped=None) == -1
     assert gate(norm_sq=odd2) == -1 and b"misaligned" in L.rn_last_error()
     assert gate(gate_dev=odd2) == -1 and gate(skipped=odd4) == -1 and b"misaligned" in L.rn_last_error()
-
+    # a bit and its pointers in disagreement, either way round; the two gates together; an unknown bit; no bit at all
+    lr = dict(schedule=train.LRSchedule("constant", 0.1).struct(), step_dev=q, lr_dev=q)
+    ema = dict(ema_decay=0.5, ema_warmup=1, ema_updates_dev=q, ema_dev=q)
+    accum = dict(accumulate_steps=2, micro_dev=q, accum_dev=q)
+    for bit, fields in ((_rn.CTL_F_LR, lr), (_rn.CTL_F_EMA, ema), (_rn.CTL_F_ACCUM, accum)):
+        assert gate(**fields) == -1 and b"only with it" in L.rn_last_error()                       # pointers set, bit clear
+        for name in fields:
+            if name.endswith("_dev"):
+                assert step_control(features=bit, **dict(fields, **{name: None})) == -1 and b"only with it" in L.rn_last_error()
+    assert step_control(features=_rn.CTL_F_LR, norm_sq=q, gate_dev=q, skipped_dev=q, **lr) == -1 and b"GUARD" in L.rn_last_error()
+    assert gate(features=_rn.CTL_F_GUARD | _rn.CTL_F_ACCUM, **accum) == -1 and b"ACCUM goes with no GUARD" in L.rn_last_error()
+    assert gate(features=_rn.CTL_F_GUARD | 16) == -1 and b"unknown feature bit" in L.rn_last_error()
+    assert step_control(features=0) == -1 and b"no feature" in L.rn_last_error()
+    assert L.rn_step_control_eval(None, None) == -1 and b"null descriptor" in L.rn_last_error()
     def step(kind=0, state2=None, count=1024, lr_dev=None, clip_norm=0.0, norm_sq=None, step=1, ema=None, ema_dev=None, w=q, gate_dev=q):
         f = (_rn.OPT_F_GATE | (_rn.OPT_F_CLIP if clip_norm > 0 else 0) | (_rn.OPT_F_LRDEV if lr_dev is not None else 0)
              | (_rn.OPT_F_EMA if None not in (ema, ema_dev) else 0))

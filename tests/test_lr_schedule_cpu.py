@@ -119,13 +119,14 @@ def test_default_total_steps_at_or_below_the_warmup_is_refused():
 
 
 def test_c_entry_checks_its_arguments_before_any_launch():
-    """rn_lr_schedule_eval / rn_optimizer_update (NORM + LRDEV): a bad descriptor is RN_EINVAL with a message (no device here; 8 stands
-    for "some non-null pointer")."""
+    """rn_step_control_eval (LR) / rn_optimizer_update (NORM + LRDEV): a bad descriptor is RN_EINVAL with a message (no device here; 8
+    stands for "some non-null pointer")."""
     import _rn
+    from helpers import step_control
     L = _rn.lib()
     p = ctypes.c_void_p(8)
 
-    def call(name="cosine", **over):
+    def lr(step_dev=p, lr_dev=p, opt_kind=0, name="cosine", **over):
         d = _schedule(name).struct()
         for k, v in over.items():
             if k == "boundaries":
@@ -133,11 +134,14 @@ def test_c_entry_checks_its_arguments_before_any_launch():
                     d.boundaries[i] = b
             else:
                 setattr(d, k, v)
-        return L.rn_lr_schedule_eval(d, p, p, 0, None)
+        return step_control(features=_rn.CTL_F_LR, optimizer_kind=opt_kind, schedule=d, step_dev=step_dev, lr_dev=lr_dev)
 
-    assert L.rn_lr_schedule_eval(_schedule("cosine").struct(), None, p, 0, None) == -1 and b"lr_schedule_eval" in L.rn_last_error()
-    assert L.rn_lr_schedule_eval(_schedule("cosine").struct(), p, None, 0, None) == -1
-    assert L.rn_lr_schedule_eval(_schedule("cosine").struct(), p, p, 3, None) == -1          # optimizer kind
+    def call(name="cosine", **over):
+        return lr(name=name, **over)
+
+    assert lr(step_dev=None) == -1 and b"step_control" in L.rn_last_error()
+    assert lr(lr_dev=None) == -1
+    assert lr(opt_kind=3) == -1                                                              # optimizer kind
     assert call(kind=3) == -1
     assert call(total_steps=2) == -1 and b"total_steps" in L.rn_last_error()                 # T == W
     assert call(total_steps=0) == -1

@@ -4,7 +4,7 @@ timing loop), momentum at a constant rate, with and without the guard against no
     --mode plain          no clipping: the one-graph step as it has always been
     --mode clip           Trainer(grad_clip_norm=C), default C = 1.0
     --guard               Trainer(skip_nonfinite=True) on top of either (not with --tree of a commit from before the guard):
-                          clipped, one more one-thread kernel (rn_finite_gate_eval) between the norm's finalize and the update;
+                          clipped, the one-thread control launch (rn_step_control_eval) between the norm's finalize and the update;
                           unclipped, the norm pass of its own (8 B per parameter) that the fused update otherwise spares
 
 One measurement per process; prints one JSON line.  --tree DIR imports the package (and its librn_hip.so) from another checkout
