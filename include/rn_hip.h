@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 419
+#define RN_API_VERSION 420
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -626,6 +626,44 @@ int rn_loss_fwd(const rn_loss_seg* segs, int nseg, int num_classes, int mode, fl
 /* d(g_cls*class_loss + g_reg*regr_loss)/d(logits); g_* are device scalars (upstream grads). */
 int rn_loss_bwd(const rn_loss_seg* segs, int nseg, int num_classes, int mode, const float* stats,
                 const float* g_cls, const float* g_reg, rn_stream_t stream);
+
+/* ------------------------------------------------------------------ loss as a weighted sum of terms
+ * Replaces classification_loss (losses.py:113-141) as a LIST of terms, the one the reference's author edits by commenting lines in
+ * and out: class loss = sum over the set terms of weight * term.  Over the M trainable rows, p = sigmoid(z), per class I = sum l p,
+ * L = sum l, P = sum p, s = the term's smooth:
+ *   RN_LT_BCE           mean_{M,C} sigmoid_cross_entropy_with_logits                                (losses.py:124-125)
+ *   RN_LT_BALANCED_BCE  (1/(M C)) sum_c (wp_c B1_c + wn_c B0_c), wp_c = (M - L_c)/M, wn_c = L_c/M, B1_c / B0_c = the sum of the
+ *                       cross entropy where l == 1 / l != 1       (balanced_sigmoid_cross_entropy_with_logits, losses.py:96-110, axis 0)
+ *   RN_LT_DICE          mean_c 1 - (2 I + s)/(L + P + s)                                            (dice_loss, losses.py:50-60, :130)
+ *   RN_LT_FIXED_IOU     mean_c 1 - (I + s)/(L + P - I + s)                                          (fixed_iou_loss, losses.py:63-73, :136)
+ *   RN_LT_JACCARD       mean_c (1 - (I + s)/(L + P - I + s)) s: s times fixed_iou(s); 0 for s = 0   (jaccard_loss, losses.py:37-47, :133)
+ *   RN_LT_FOCAL         sum focal / max(#fg, 1), focus 2, alpha 0.25, eps 1e-7                      (losses.py:6-15, :119-122)
+ * The smooths of the reference's call sites (:130, :133, :136): dice 0, jaccard 1, fixed_iou 1e-7.
+ * focal_softmax_cross_entropy_with_logits (losses.py:18-34, "check if this is correct") is not covered.
+ * Regression loss, #fg, masking rule, segments and the two-pass structure are those of rn_loss_fwd / rn_loss_bwd above.
+ * With M = 0 the two cross-entropy terms are NaN (0/0), as in the reference and in rn_loss_fwd.
+ *
+ * The descriptor is read before the call returns.  RN_EINVAL: null descriptor; no term or an unknown bit set; the weight of a
+ * set term not finite or <= 0; a smooth not finite or < 0; weight or smooth of a clear term not 0; jaccard's weight * smooth
+ * not finite.
+ * A descriptor equal to {BCE 1, DICE 1, s_dice 0} or {FOCAL 1} runs the kernels of rn_loss_fwd / rn_loss_bwd in that mode:
+ * losses, stats [0, 8 + 3C) and gradients are bit-identical to them (stats [8 + 3C, 8 + 5C) are not written then); the
+ * environment variable RN_LOSS_TERMS_GENERAL=1 runs the general kernels for these two as well (measurements).
+ * stats: the layout above, then [8 + 3C + c] = B1_c and [8 + 4C + c] = B0_c; the general kernels write zeros there without
+ * RN_LT_BALANCED_BCE, the two descriptors that run the kernels of rn_loss_fwd leave these 2C entries as the caller passed them. */
+enum rn_loss_term { RN_LT_BCE = 1, RN_LT_BALANCED_BCE = 2, RN_LT_DICE = 4, RN_LT_JACCARD = 8, RN_LT_FIXED_IOU = 16, RN_LT_FOCAL = 32 };
+typedef struct rn_loss_terms {
+  uint32_t terms;        /* OR of rn_loss_term */
+  float w_bce, w_balanced_bce, w_dice, w_jaccard, w_fixed_iou, w_focal;   /* > 0 for a set term, 0 for a clear one */
+  float s_dice, s_jaccard, s_fixed_iou;                                   /* >= 0; 0 for a clear term */
+} rn_loss_terms;
+size_t rn_loss_terms_stats_floats(int num_classes);     /* RN_LOSS_STATS_HEADER + 5 C */
+/* 0 (and rn_last_error) for a descriptor rn_loss_terms_fwd would refuse */
+size_t rn_loss_terms_workspace(const rn_loss_seg* segs, int nseg, int num_classes, const rn_loss_terms* t);
+int rn_loss_terms_fwd(const rn_loss_seg* segs, int nseg, int num_classes, const rn_loss_terms* t, float* stats,
+                      float* class_loss_out, float* regr_loss_out, void* workspace, size_t workspace_bytes, rn_stream_t stream);
+int rn_loss_terms_bwd(const rn_loss_seg* segs, int nseg, int num_classes, const rn_loss_terms* t, const float* stats,
+                      const float* g_cls, const float* g_reg, rn_stream_t stream);
 
 /* ------------------------------------------------------------------ running training metrics
  * Replaces build_metrics (train.py:137-161): the streaming tf.metrics of a training run -- the means of the total, class,

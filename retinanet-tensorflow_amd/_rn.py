@@ -22,7 +22,7 @@ LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
 CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
-API_VERSION = 419        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 420        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -209,6 +209,17 @@ class LossSeg(C.Structure):
                 ("d_reg_pred", C.c_void_p), ("rows", C.c_int64)]
 
 
+# enum rn_loss_term; the names are those of losses.parse_class_loss and of the w_ / s_ fields below
+LOSS_TERM = {"bce": 1, "balanced_bce": 2, "dice": 4, "jaccard": 8, "fixed_iou": 16, "focal": 32}
+
+
+class LossTerms(C.Structure):
+    """rn_loss_terms (passed by pointer, read before the call returns): weight and smooth of a clear term stay 0."""
+    _fields_ = [("terms", C.c_uint32), ("w_bce", C.c_float), ("w_balanced_bce", C.c_float), ("w_dice", C.c_float),
+                ("w_jaccard", C.c_float), ("w_fixed_iou", C.c_float), ("w_focal", C.c_float),
+                ("s_dice", C.c_float), ("s_jaccard", C.c_float), ("s_fixed_iou", C.c_float)]
+
+
 class MetricsSeg(C.Structure):
     """rn_metrics_seg: one pyramid level of rn_train_metrics_pass"""
     _fields_ = [("cls_logit", C.c_void_p), ("cls_label", C.c_void_p), ("reg_pred", C.c_void_p), ("reg_label", C.c_void_p),
@@ -252,6 +263,7 @@ SYMBOLS = [
     "rn_pack_weights_f16", "rn_pack_weights_f16_bytes", "rn_cast_f32_to_f16", "rn_pad_cast_rgb_f16", "rn_conv2d_fwd_f16", "rn_conv2d_f16_fold_rows", "rn_conv2d_fwd_f16_fold", "rn_group_norm_finalize", "rn_group_norm_apply_f16", "rn_group_norm_apply_res_f16", "rn_maxpool_fwd_f16", "rn_maxpool_gn_fwd_f16", "rn_upsample_add_fwd_f16",
     "rn_act_fwd_f16", "rn_flip_width", "rn_dropout", "rn_dropout_strided", "rn_maxpool_fwd", "rn_maxpool_bwd", "rn_maxpool_bwd_arg", "rn_avgpool_fwd", "rn_avgpool_bwd",
     "rn_loss_workspace", "rn_loss_fwd", "rn_loss_bwd",
+    "rn_loss_terms_stats_floats", "rn_loss_terms_workspace", "rn_loss_terms_fwd", "rn_loss_terms_bwd",
     "rn_iou", "rn_anchor_assign", "rn_anchor_assign_levels", "rn_anchor_assign_levels_pair", "rn_decode_boxes", "rn_detect_workspace", "rn_detect",
     "rn_boxes_decode", "rn_nms_classwise_workspace", "rn_nms_classwise",
     "rn_optimizer_workspace", "rn_grad_norm_l2reg", "rn_optimizer_update", "rn_counter_add", "rn_add_segs",
@@ -411,6 +423,14 @@ def lib():
                                   C.c_void_p]
         L.rn_loss_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]
+        L.rn_loss_terms_stats_floats.restype = C.c_size_t
+        L.rn_loss_terms_stats_floats.argtypes = [C.c_int]
+        L.rn_loss_terms_workspace.restype = C.c_size_t
+        L.rn_loss_terms_workspace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LossTerms)]
+        L.rn_loss_terms_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LossTerms), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rn_loss_terms_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LossTerms), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
         L.rn_iou.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_anchor_assign.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + \
                                       [C.c_void_p] * 4 + [C.c_void_p]

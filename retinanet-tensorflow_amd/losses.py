@@ -9,14 +9,85 @@ variant :6-15 that BASELINE's north_star names).
 ``set_trainable_masks`` / the ``trainable_masks`` argument.  One fused HIP kernel pair
 (csrc/loss.hip) computes BCE + dice (or focal) and the Huber box loss over every anchor of
 every level, forward and backward.
+
+``mode`` may also be a class-loss SPEC: the reference's ``classification_loss`` (losses.py:113-141) is a list of terms its author
+comments in and out; a spec names the terms to sum, each with a weight and, for the overlap terms, a smooth
+(``parse_class_loss``; csrc/loss_terms.hip).
 """
+import collections
+import math
+
 import ops
 
 LOSS_MODE = 'bce_dice'        # 'bce_dice' = live reference path; 'focal' = losses.py:6-15 + :119-122
 
+TERM_NAMES = ('bce', 'balanced_bce', 'dice', 'jaccard', 'fixed_iou', 'focal')
+# the smooths of the reference's call sites (losses.py:130, :133, :136); the other terms have none
+DEFAULT_SMOOTH = {'dice': 0.0, 'jaccard': 1.0, 'fixed_iou': 1e-7}
+
+Term = collections.namedtuple('Term', 'name weight smooth')        # smooth: None for a term that has none
+
+
+class ClassLoss(tuple):
+    """The parsed spec: a tuple of Term in the order given."""
+
+    def spec(self):
+        """The spec in full (every weight and smooth written out); parse_class_loss(x.spec()) == x."""
+        return '+'.join('%s:%r' % (t.name, t.weight) + ('' if t.smooth is None else ':%r' % t.smooth) for t in self)
+
+    def describe(self):
+        return ' + '.join('%g * %s' % (t.weight, t.name) + ('' if t.smooth is None else '(smooth %g)' % t.smooth) for t in self)
+
+    def struct(self):
+        """The rn_loss_terms descriptor (include/rn_hip.h)."""
+        import _rn
+        d = _rn.LossTerms()
+        for t in self:
+            d.terms |= _rn.LOSS_TERM[t.name]
+            setattr(d, 'w_' + t.name, t.weight)
+            if t.smooth is not None:
+                setattr(d, 's_' + t.name, t.smooth)
+        return d
+
+
+def parse_class_loss(spec):
+    """SPEC = TERM[+TERM...], TERM = NAME[:WEIGHT[:SMOOTH]]; NAME one of TERM_NAMES, each at most once; WEIGHT > 0 (default 1);
+    SMOOTH >= 0 only for dice, jaccard and fixed_iou (defaults 0, 1, 1e-7: the reference's call sites).  Class loss =
+    sum WEIGHT * term.  E.g. 'bce+jaccard', 'balanced_bce+dice:0.5', 'bce+dice:1:1+fixed_iou:0.3:1e-7'.  jaccard(s) is
+    s * fixed_iou(s) (losses.py:37-47 against :63-73), so jaccard:W:0 is identically 0.  Raises ValueError naming the token."""
+    if isinstance(spec, ClassLoss):
+        return spec
+    if not isinstance(spec, str) or not spec.strip():
+        raise ValueError('class loss spec %r: empty' % (spec,))
+    terms = []
+    for token in spec.split('+'):
+        def bad(why):
+            return ValueError('class loss spec %r: term %r: %s' % (spec, token, why))
+        fields = token.strip().split(':')
+        name = fields[0].strip()
+        if name not in TERM_NAMES:
+            raise bad('unknown name (one of %s)' % ', '.join(TERM_NAMES))
+        if any(t.name == name for t in terms):
+            raise bad('given twice')
+        if len(fields) > (3 if name in DEFAULT_SMOOTH else 2):
+            raise bad('NAME:WEIGHT:SMOOTH at the most' if name in DEFAULT_SMOOTH else 'takes no smooth (NAME:WEIGHT)')
+        try:
+            weight = float(fields[1]) if len(fields) > 1 else 1.0
+            smooth = float(fields[2]) if len(fields) > 2 else DEFAULT_SMOOTH.get(name)
+        except ValueError:
+            raise bad('weight and smooth are numbers')
+        if not (math.isfinite(weight) and weight > 0.0):
+            raise bad('the weight must be finite and > 0')
+        if smooth is not None and not (math.isfinite(smooth) and smooth >= 0.0):
+            raise bad('the smooth must be finite and >= 0')
+        if name == 'jaccard' and weight * smooth > 3.4e38:
+            raise bad('weight * smooth (the scale of the term) overflows float32')
+        terms.append(Term(name, weight, smooth))
+    return ClassLoss(terms)
+
 
 def loss(labels, logits, trainable_masks=None, mode=None, name='loss', return_stats=False):
-    """(class_loss, regr_loss) as 0-dim tensors (losses.py:155-175)."""
+    """(class_loss, regr_loss) as 0-dim tensors (losses.py:155-175).  mode: 'bce_dice', 'focal', or a class-loss spec / ClassLoss."""
     mode = mode or LOSS_MODE
     keys = list(logits.regression.keys())
     if trainable_masks is None:

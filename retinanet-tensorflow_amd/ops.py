@@ -1088,14 +1088,20 @@ class _DetectionLoss(torch.autograd.Function):
             assert z.shape == l.shape and z.shape[-1] == num_classes and z.numel() == m.numel() * num_classes
         L = _rn.lib()
         dev = cls_logits[0].device
-        stats = torch.empty((_rn.LOSS_STATS_HEADER + 3 * num_classes,), dtype=torch.float32, device=dev)
         segs = _loss_segs(cls_logits, cls_labels, reg_preds, reg_labels, masks, None, None)
-        need = L.rn_loss_workspace(segs, n, num_classes)
-        ws = _rn.workspace(need, dev)
         class_loss = torch.empty((), dtype=torch.float32, device=dev)     # stand-alone scalars written by the kernel itself
         regr_loss = torch.empty((), dtype=torch.float32, device=dev)      # (no copies of stats[0], stats[1])
-        _rn.check(L.rn_loss_fwd(segs, n, num_classes, _rn.LOSS_MODE[mode], _rn.f32(stats), _rn.f32(class_loss), _rn.f32(regr_loss),
-                                ws.data_ptr(), ws.numel(), _rn.stream()), "rn_loss_fwd")
+        if mode in _rn.LOSS_MODE:
+            stats = torch.empty((_rn.LOSS_STATS_HEADER + 3 * num_classes,), dtype=torch.float32, device=dev)
+            ws = _rn.workspace(L.rn_loss_workspace(segs, n, num_classes), dev)
+            _rn.check(L.rn_loss_fwd(segs, n, num_classes, _rn.LOSS_MODE[mode], _rn.f32(stats), _rn.f32(class_loss), _rn.f32(regr_loss),
+                                    ws.data_ptr(), ws.numel(), _rn.stream()), "rn_loss_fwd")
+        else:       # a losses.ClassLoss: the weighted sum of terms (csrc/loss_terms.hip)
+            desc = mode.struct()
+            stats = torch.empty((L.rn_loss_terms_stats_floats(num_classes),), dtype=torch.float32, device=dev)
+            ws = _rn.workspace(L.rn_loss_terms_workspace(segs, n, num_classes, C.byref(desc)), dev)
+            _rn.check(L.rn_loss_terms_fwd(segs, n, num_classes, C.byref(desc), _rn.f32(stats), _rn.f32(class_loss), _rn.f32(regr_loss),
+                                          ws.data_ptr(), ws.numel(), _rn.stream()), "rn_loss_terms_fwd")
         ctx.mode, ctx.num_classes, ctx.n = mode, num_classes, n
         ctx.save_for_backward(stats, *cls_logits, *reg_preds, *cls_labels, *reg_labels, *masks)
         ctx.mark_non_differentiable(stats)
@@ -1121,14 +1127,24 @@ class _DetectionLoss(torch.autograd.Function):
         dcls = [torch.empty_like(z) for z in cls_logits]
         dreg = [torch.empty_like(r) for r in reg_preds]
         segs = _loss_segs(cls_logits, cls_labels, reg_preds, reg_labels, masks, dcls, dreg)
-        _rn.check(_rn.lib().rn_loss_bwd(segs, n, ctx.num_classes, _rn.LOSS_MODE[ctx.mode], _rn.f32(stats),
-                                        _rn.f32(g_cls), _rn.f32(g_reg), _rn.stream()), "rn_loss_bwd")
+        if ctx.mode in _rn.LOSS_MODE:
+            _rn.check(_rn.lib().rn_loss_bwd(segs, n, ctx.num_classes, _rn.LOSS_MODE[ctx.mode], _rn.f32(stats),
+                                            _rn.f32(g_cls), _rn.f32(g_reg), _rn.stream()), "rn_loss_bwd")
+        else:
+            _rn.check(_rn.lib().rn_loss_terms_bwd(segs, n, ctx.num_classes, C.byref(ctx.mode.struct()), _rn.f32(stats),
+                                                  _rn.f32(g_cls), _rn.f32(g_reg), _rn.stream()), "rn_loss_terms_bwd")
         return (None, None, None) + tuple(dcls) + tuple(dreg) + (None,) * (3 * n)
 
 
 def detection_loss(cls_logits, reg_preds, cls_labels, reg_labels, trainable_masks, num_classes, mode="bce_dice"):
-    """Lists over pyramid levels (P3..P7 order).  Returns (class_loss, regr_loss, stats)."""
+    """Lists over pyramid levels (P3..P7 order).  Returns (class_loss, regr_loss, stats).  mode: 'bce_dice' / 'focal'
+    (rn_loss_fwd / rn_loss_bwd), or a class-loss spec / losses.ClassLoss (rn_loss_terms_fwd / rn_loss_terms_bwd; stats then has
+    rn_loss_terms_stats_floats entries, the last 2 C of them -- B1_c, B0_c -- unwritten for a spec equal to 'bce+dice' or 'focal:1',
+    which runs the existing kernels)."""
     n = len(cls_logits)
+    if isinstance(mode, str) and mode not in _rn.LOSS_MODE:
+        import losses
+        mode = losses.parse_class_loss(mode)
     return _DetectionLoss.apply(mode, num_classes, n, *cls_logits, *reg_preds, *cls_labels, *reg_labels,
                                 *trainable_masks)
 

@@ -576,7 +576,9 @@ class Trainer(object):
                 "call torch.cuda.set_device(%d) before building the Trainer" % self.device.index
         # (without an lr_schedule Adam's bias-corrected learning rate is a fresh launch argument every step: its update -- and
         # RMSProp's -- is then launched per step, outside the captured segments, also with use_graph=True)
-        self.loss_mode = loss_mode
+        # loss_mode: 'bce_dice' / 'focal' (None: losses.LOSS_MODE), or a class-loss spec (losses.parse_class_loss: a weighted sum of the reference's terms),
+        # parsed here so that a bad one fails before anything is built; the loss stays two nodes of the step's graph either way
+        self.loss_mode = loss_mode if (loss_mode is None or loss_mode in _rn.LOSS_MODE) else losses.parse_class_loss(loss_mode)
         self.arena = ParamArena(net, self.device)
         # lr_schedule (LRSchedule): the rate lives on the device and advances inside the step (Optimizer docstring); None: the
         # constant `learning_rate`, a launch argument
@@ -1292,6 +1294,11 @@ def build_parser():
                         default='mobilenet_v2')
     parser.add_argument('--optimizer', type=str, choices=['momentum', 'adam', 'rmsprop'], default='momentum')
     parser.add_argument('--loss', type=str, choices=['bce_dice', 'focal'], default='bce_dice')
+    parser.add_argument('--class-loss', type=str, default=None, metavar='SPEC',
+                        help='the class loss as a weighted sum of the terms of the reference\'s classification_loss: '
+                             'NAME[:WEIGHT[:SMOOTH]] joined by +, NAME one of %s, SMOOTH for dice / jaccard / fixed_iou only '
+                             '(defaults 0 / 1 / 1e-7), e.g. bce+jaccard or balanced_bce+dice:0.5; not with --loss focal'
+                             % ', '.join(losses.TERM_NAMES))
     parser.add_argument('--steps-per-epoch', type=int, default=None,
                         help='default: 100 for shapes, NUM for shapes PATH NUM SIZE, one pass of the shard for a file dataset')
     parser.add_argument('--shape-runs', type=int, default=None,
@@ -1360,6 +1367,19 @@ def train_metrics_suffix(res):
     return (' | mean total %.4f class %.4f regr %.4f reg %.4f class_iou %.4f regr_iou %.4f over %d steps' % (
         res['total_loss'], res['class_loss'], res['regr_loss'], res['regularization_loss'], res['class_iou'], res['regr_iou'],
         res['steps']) + (' (%d non-finite left out)' % res['nonfinite_steps'] if res['nonfinite_steps'] > 0 else ''))
+
+
+def class_loss_flag_error(args):
+    """What is wrong with --class-loss as given (checked before any dataset or device is touched), or None."""
+    if args.class_loss is None:
+        return None
+    if args.loss != 'bce_dice':
+        return '--class-loss with --loss %s: the spec names every term of the class loss, leave --loss out' % args.loss
+    try:
+        losses.parse_class_loss(args.class_loss)
+    except ValueError as e:
+        return '--class-loss: %s' % e
+    return None
 
 
 def accumulate_flag_error(args):
@@ -1514,6 +1534,8 @@ def main(argv=None):
         parser.error(accumulate_flag_error(args))
     if guard_flag_error(args):
         parser.error(guard_flag_error(args))
+    if class_loss_flag_error(args):
+        parser.error(class_loss_flag_error(args))
     K = args.samples_per_step
     if K != 1 and not files:
         parser.error('--samples-per-step groups raw uint8 image files: it needs --dataset pascal ... or coco ...')
@@ -1587,11 +1609,13 @@ def main(argv=None):
     except ValueError as e:
         parser.error(str(e))
     trainer = Trainer(net, levels, optimizer=args.optimizer, learning_rate=args.learning_rate,
-                      grad_clip_norm=args.grad_clip_norm, loss_mode=args.loss, device=dev, use_graph=not args.no_graph,
+                      grad_clip_norm=args.grad_clip_norm, loss_mode=args.class_loss or args.loss, device=dev, use_graph=not args.no_graph,
                       input_fn=feed, **({'lr_schedule': lr_schedule} if lr_schedule is not None else {}),
                       **({'ema_decay': args.ema_decay, 'ema_warmup': not args.ema_no_warmup} if args.ema_decay is not None else {}),
                       **({'accumulate_steps': A} if A > 1 else {}), **({'skip_nonfinite': True} if args.skip_nonfinite else {}),
                       **({'train_metrics': True} if args.train_metrics else {}))
+    if args.class_loss is not None and rank == 0:
+        print('class loss: %s' % trainer.loss_mode.describe(), flush=True)
 
     def skipped():
         return check_nonfinite_limit(trainer, args.nonfinite_limit)
