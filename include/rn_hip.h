@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 420
+#define RN_API_VERSION 421
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -148,6 +148,78 @@ int rn_conv2d_bwd(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, floa
 size_t rn_conv2d_bias_grad_workspace(int cout);
 int rn_conv2d_bias_grad(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, float* dbias, void* workspace,
                         size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer);
+
+/* ------------------------------------------------------------------ what a convolution call launches (host only)
+ * rn_conv2d_plan reports the kernels one rn_conv2d_fwd / _fwd_stats / _dgrad / _wgrad / _bwd call with the same arguments
+ * launches.  It is the decision the entry points launch from: conv_fwd_impl, conv_dgrad_impl, conv_wgrad_impl and the body of
+ * rn_conv2d_bwd (csrc/conv_gemm.hip) fill an rn_conv_plan_call and launch from it; the query stops them before the first
+ * launch.  It runs on the host, touches no device and follows no data pointer: segs[].x / wgt / y / dy / dx / bias, dw and
+ * workspace are only compared with NULL where the entry point does that.  Returns what the launch would return for the same
+ * arguments (RN_EINVAL / RN_EUNSUPPORTED / RN_EWORKSPACE), RN_EINVAL for a NULL plan or an unknown op.
+ *   op               RN_CONV_FWD, RN_CONV_FWD_STATS (stats_groups = the GroupNorm's group count; RN_EUNSUPPORTED where
+ *                    rn_conv2d_stats_rows returns 0), RN_CONV_DGRAD, RN_CONV_WGRAD (accumulate, defer != 0: a defer list is
+ *                    passed), RN_CONV_BWD (defer likewise)
+ *   workspace[_bytes] what the caller will pass to the entry point (split-K and the patch matrix are declined without it)
+ * Environment switches, as the entry points read them.  At every call: RN_CONV_CFG, RN_WGRAD_CFG, RN_WGRAD_SPLITS,
+ * RN_NO_SPLITK, RN_NO_PHASE_DGRAD.  Once per process (first use): RN_STEM_DIRECT, RN_X3_CONV1X1, RN_X3_IM2COL,
+ * RN_GCONV_DIRECT, RN_NO_MERGED_BWD, RN_X3_IM2COL_PIECE_MB.  The product mode (rn_set_product_mode) is read at every call.
+ * rn_gemm_batched_plan: the same for rn_gemm_batched (the fp32 kernels in batched mode, or the split-bf16 product). */
+enum rn_conv_op { RN_CONV_FWD = 0, RN_CONV_FWD_STATS = 1, RN_CONV_DGRAD = 2, RN_CONV_WGRAD = 3, RN_CONV_BWD = 4 };
+enum rn_conv_path {
+  RN_CONV_PATH_NONE = 0,
+  RN_CONV_PATH_DIRECT_GROUPED = 1, /* grouped_conv.hip: 3x3 / stride 1, 4 / 8 / 16 / 32 channels per group */
+  RN_CONV_PATH_STEM = 2,           /* stem_conv_fwd_kernel */
+  RN_CONV_PATH_X3_1X1 = 3,         /* split-bf16 product on x itself (gemm_x3.hip) */
+  RN_CONV_PATH_X3_PATCH = 4,       /* split-bf16 product of a patch matrix (im2col.hip) */
+  RN_CONV_PATH_FP32 = 5,           /* the fp32 implicit GEMM of conv_gemm.hip */
+  RN_CONV_PATH_MERGED_BWD = 6      /* conv_bwd_kernel: data-gradient tiles and weight-gradient splits in one launch */
+};
+enum rn_conv_load { RN_CONV_LOAD_SCALAR = 0, RN_CONV_LOAD_VEC4 = 1, RN_CONV_LOAD_VEC4_TAP = 2 /* tap-uniform K tiles */ };
+enum rn_conv_reduce { RN_CONV_REDUCE_NONE = 0, RN_CONV_REDUCE_LAUNCHED = 1, RN_CONV_REDUCE_DEFERRED = 2 };
+/* why rn_conv2d_bwd runs as two calls */
+enum rn_conv_unmerged {
+  RN_CONV_MERGED = 0,
+  RN_CONV_UNMERGED_SWITCH = 1, /* RN_NO_MERGED_BWD */
+  RN_CONV_UNMERGED_X3_1X1 = 2, /* the split-bf16 1x1 kernels take the conv */
+  RN_CONV_UNMERGED_DIRECT = 3, /* the direct grouped kernels take it */
+  RN_CONV_UNMERGED_PATCH = 4,  /* the patch-matrix path takes it */
+  RN_CONV_UNMERGED_SHAPE = 5   /* the fp32 plans do not fit the merged kernel: more than 4 (pseudo-)segments, scalar loads, a
+                                  data-gradient tile other than 64 x 64, phase decomposition */
+};
+typedef struct rn_conv_plan_call {
+  int32_t path;            /* enum rn_conv_path */
+  /* fp32 kernels (path FP32, and both halves of MERGED_BWD) */
+  int32_t cfg;             /* tile shape: 0 128x128, 1 128x64, 2 64x64, 3 128x32 */
+  int32_t load;            /* enum rn_conv_load */
+  int32_t nsplit;          /* fwd / dgrad: split-K ranges (1: none).  wgrad: splits of the pixel range, all segments */
+  int32_t ksplit;          /* fwd / dgrad: K tiles per range (0: no split-K).  wgrad: `chunk`, pixels per split */
+  int32_t blocks;          /* grid size of the conv kernel */
+  int32_t grouped;         /* groups > 1 */
+  int32_t batched;         /* number of batched products (rn_gemm_batched; 1 otherwise) */
+  /* data gradient */
+  int32_t phases;          /* stride 2: phase pseudo-segments (0: not decomposed) */
+  int32_t phases_no_taps;  /* ... of which see no filter tap (they store zeros) */
+  /* weight gradient */
+  int32_t windows;         /* a split is longer than the kernel's 1024-pixel table and walks its range in windows */
+  int32_t direct;          /* one split, written straight into dw (no slab, no reduction) */
+  int32_t reduce;          /* enum rn_conv_reduce: the final row reduction */
+  /* split-bf16 paths */
+  int32_t m_tile;          /* m-tile rows: 64 or 128 */
+  int32_t n_piece;         /* patch matrix, forward: samples per piece (n / n_piece pieces) */
+  int64_t patch_bytes;     /* patch matrix: its bytes (of one piece) */
+  /* RN_CONV_FWD_STATS */
+  int32_t rows_per_sample;
+  int32_t reserved_;
+} rn_conv_plan_call;
+typedef struct rn_conv_plan {
+  rn_conv_plan_call call;         /* the call (RN_CONV_BWD: path MERGED_BWD with blocks = both halves', or NONE when not merged) */
+  rn_conv_plan_call dgrad, wgrad; /* RN_CONV_BWD: the two halves (merged) / the two calls it runs instead */
+  int32_t unmerged;               /* RN_CONV_BWD: enum rn_conv_unmerged */
+  int32_t reserved_;
+} rn_conv_plan;
+int rn_conv2d_plan(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int op, int stats_groups, int accumulate, int defer,
+                   const float* dw, const void* workspace, size_t workspace_bytes, rn_conv_plan* plan);
+int rn_gemm_batched_plan(const float* A, const float* B, const float* C, int M, int K, int N, int nbatch, int b_nk, rn_conv_plan* plan);
 
 /* ------------------------------------------------------------------ deferred gradient reductions
  * Every weight-gradient entry point (rn_conv2d_wgrad, rn_conv2d_bwd, rn_depthwise_wgrad, rn_depthwise_bwd,

@@ -22,7 +22,7 @@ LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
 CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
-API_VERSION = 420        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 421        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -96,6 +96,28 @@ class WinoGnPlan(C.Structure):
     """rn_wino_gn_plan: the kernels one folded Winograd layer launches (rn_conv3x3_winograd_gn_plan, host only)"""
     _fields_ = [("fwd", WinoGnPlanCall), ("bwd", WinoGnPlanCall), ("tiles", C.c_int32), ("chunks", C.c_int32),
                 ("partial_chunk", C.c_int32), ("u_frag", C.c_int32)]
+
+
+class ConvPlanCall(C.Structure):
+    """rn_conv_plan_call: the kernels one convolution call launches"""
+    _fields_ = [("path", C.c_int32), ("cfg", C.c_int32), ("load", C.c_int32), ("nsplit", C.c_int32), ("ksplit", C.c_int32),
+                ("blocks", C.c_int32), ("grouped", C.c_int32), ("batched", C.c_int32), ("phases", C.c_int32),
+                ("phases_no_taps", C.c_int32), ("windows", C.c_int32), ("direct", C.c_int32), ("reduce", C.c_int32),
+                ("m_tile", C.c_int32), ("n_piece", C.c_int32), ("patch_bytes", C.c_int64), ("rows_per_sample", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+class ConvPlan(C.Structure):
+    """rn_conv_plan: what rn_conv2d_fwd / _fwd_stats / _dgrad / _wgrad / _bwd launch (rn_conv2d_plan, host only)"""
+    _fields_ = [("call", ConvPlanCall), ("dgrad", ConvPlanCall), ("wgrad", ConvPlanCall), ("unmerged", C.c_int32), ("reserved_", C.c_int32)]
+
+
+# enum rn_conv_op / rn_conv_path / rn_conv_load / rn_conv_reduce / rn_conv_unmerged
+CONV_OPS = {"fwd": 0, "fwd_stats": 1, "dgrad": 2, "wgrad": 3, "bwd": 4}
+CONV_PATHS = {0: None, 1: "direct_grouped", 2: "stem", 3: "x3_1x1", 4: "x3_patch", 5: "fp32", 6: "merged_bwd"}
+CONV_LOADS = {0: "scalar", 1: "vec4", 2: "vec4_tap"}
+CONV_REDUCES = {0: None, 1: "launched", 2: "deferred"}
+CONV_UNMERGED = {0: None, 1: "switch", 2: "x3_1x1", 3: "direct_grouped", 4: "x3_patch", 5: "shape"}
 
 
 class ReduceDesc(C.Structure):
@@ -251,7 +273,7 @@ SYMBOLS = [
     "rn_conv2d_fwd_workspace", "rn_conv2d_dgrad_workspace",
     "rn_zero", "rn_conv2d_fwd", "rn_conv2d_stats_rows", "rn_conv2d_fwd_stats", "rn_conv2d_dropout_rows", "rn_conv2d_fwd_dropout", "rn_depthwise_stats_rows", "rn_depthwise_fwd_stats", "rn_group_norm_rows_ok",
     "rn_conv2d_dgrad", "rn_conv2d_wgrad_workspace", "rn_conv2d_wgrad", "rn_conv2d_bwd",
-    "rn_conv2d_bias_grad_workspace", "rn_conv2d_bias_grad", "rn_conv3x3_winograd_workspace", "rn_conv3x3_winograd",
+    "rn_conv2d_bias_grad_workspace", "rn_conv2d_bias_grad", "rn_conv2d_plan", "rn_gemm_batched_plan", "rn_conv3x3_winograd_workspace", "rn_conv3x3_winograd",
     "rn_conv3x3_winograd_wgrad_workspace", "rn_conv3x3_winograd_wgrad", "rn_conv3x3_winograd_keep_bytes",
     "rn_conv3x3_winograd_bwd_workspace", "rn_conv3x3_winograd_bwd", "rn_flush_reductions", "rn_gemm_batched",
     "rn_winograd_bwd_products_workspace", "rn_winograd_bwd_products", "rn_wino_gn_rows", "rn_conv3x3_winograd_gn", "rn_conv3x3_winograd_gn_bwd", "rn_conv3x3_winograd_gn_bwd_wgrad", "rn_conv3x3_winograd_gn_plan", "rn_reduce_rows", "rn_resize_bilinear_normalize", "rn_resize_pair_u8",
@@ -326,6 +348,9 @@ def lib():
         L.rn_depthwise_stats_rows.argtypes = [C.c_int] * 7 + [C.c_void_p]
         L.rn_group_norm_rows_ok.argtypes = [C.c_int] * 4
         L.rn_depthwise_fwd_stats.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
+        L.rn_conv2d_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.POINTER(ConvPlan)]
+        L.rn_gemm_batched_plan.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.POINTER(ConvPlan)]
         L.rn_conv2d_fwd_workspace.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rn_conv2d_dgrad_workspace.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rn_conv2d_bwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -925,10 +925,23 @@ struct Planned {
 struct Scratch { void* ws; size_t bytes; size_t* need_out; };
 // rows request of rn_conv2d_fwd_stats: `rows` the caller's buffer, or (dry run) layout_out = the layout + bytes_out (0: cannot)
 struct StatReq { const rn_gn_rows* rows; int groups; rn_gn_rows* layout_out; size_t* bytes_out; };
+// rn_conv2d_plan's hook: every *_impl decides into an rn_conv_plan_call of its own and launches from it; `out` receives a copy
+// of the decision, `dry` returns where the first launch would be (after the argument checks the launch makes)
+struct PlanOut { rn_conv_plan_call* out; bool dry; };
+const PlanOut kNoPlan = {nullptr, false};
+inline int load_variant(bool vec, bool tapu) { return tapu ? RN_CONV_LOAD_VEC4_TAP : (vec ? RN_CONV_LOAD_VEC4 : RN_CONV_LOAD_SCALAR); }
+inline void report(const PlanOut& po, const rn_conv_plan_call& pc) { if (po.out) *po.out = pc; }
+// dry run of a path whose launcher (gemm_x3.hip, grouped_conv.hip) checks the workspace itself: the status it would return
+inline int dry_workspace_status(size_t have, size_t need) {
+  if (have >= need) return RN_OK;
+  rn::set_error("conv wgrad: workspace %zu < %zu bytes", have, need);
+  return RN_EWORKSPACE;
+}
 int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, const Batch& bt, rn_stream_t stream,
-                  const Scratch& sc = Scratch{nullptr, 0, nullptr}, const StatReq& sr = StatReq{nullptr, 0, nullptr, nullptr});
+                  const Scratch& sc = Scratch{nullptr, 0, nullptr}, const StatReq& sr = StatReq{nullptr, 0, nullptr, nullptr},
+                  const PlanOut& po = kNoPlan);
 int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, const Batch& bt, rn_stream_t stream,
-                    const Scratch& sc = Scratch{nullptr, 0, nullptr}, Planned* plan = nullptr);
+                    const Scratch& sc = Scratch{nullptr, 0, nullptr}, Planned* plan = nullptr, const PlanOut& po = kNoPlan);
 
 // Tiny grids with a long reduction (the stride-2 convs that make P6 / P7, the 4x4 and 8x8 maps: 4..24 tiles x 72+
 // K-tiles) are latency-bound on a handful of CUs: split K over ~384/tiles blocks per tile and sum the partial
@@ -1016,19 +1029,30 @@ extern "C" int rn_conv2d_dgrad(const rn_conv_seg* segs, int nseg, const rn_conv_
 
 // C_b [M x N] = A_b [M x K] * B_b   for b = 0..nbatch-1 in one launch (Winograd's per-point products).
 // b_nk == 0: B_b is [K x N] (forward kernel);  b_nk != 0: B_b is [N x K] (the data-gradient kernel's layout).
-int rn::launch_batched_gemm(const float* A, const float* B, float* C, int M, int K, int N, int nbatch, int b_nk,
-                            hipStream_t st) {
-  if (rn::product_mode() == 1 && rn::gemm_x3_ok(M, K, N)) return rn::launch_batched_gemm_x3(A, B, C, M, K, N, nbatch, b_nk, st);
+namespace {
+int batched_gemm_impl(const float* A, const float* B, float* C, int M, int K, int N, int nbatch, int b_nk, hipStream_t st, const PlanOut& po) {
+  if (rn::product_mode() == 1 && rn::gemm_x3_ok(M, K, N)) {
+    rn_conv_plan_call pc = {};
+    pc.path = RN_CONV_PATH_X3_1X1; pc.batched = nbatch; pc.m_tile = rn::x3_tile_rows(M, N, nbatch);
+    report(po, pc);
+    if (po.dry) return RN_OK;
+    return rn::launch_batched_gemm_x3(A, B, C, M, K, N, nbatch, b_nk, st);
+  }
   rn_conv_seg sg = {};
   sg.n = 1; sg.h = 1; sg.w = M; sg.wgt = B;
   rn_conv_geom g1 = {1, 1, 1, b_nk ? N : K, 1};
   const Batch bt = {nbatch, (long)M * K, (long)K * N, (long)M * N};
   if (b_nk) {
     sg.dy = A; sg.dx = C; sg.cout = K;
-    return conv_dgrad_impl(&sg, 1, &g1, bt, (rn_stream_t)st);
+    return conv_dgrad_impl(&sg, 1, &g1, bt, (rn_stream_t)st, Scratch{nullptr, 0, nullptr}, nullptr, po);
   }
   sg.x = A; sg.y = C; sg.cout = N;
-  return conv_fwd_impl(&sg, 1, &g1, bt, (rn_stream_t)st);
+  return conv_fwd_impl(&sg, 1, &g1, bt, (rn_stream_t)st, Scratch{nullptr, 0, nullptr}, StatReq{nullptr, 0, nullptr, nullptr}, po);
+}
+}  // namespace
+int rn::launch_batched_gemm(const float* A, const float* B, float* C, int M, int K, int N, int nbatch, int b_nk,
+                            hipStream_t st) {
+  return batched_gemm_impl(A, B, C, M, K, N, nbatch, b_nk, st, kNoPlan);
 }
 
 namespace {
@@ -1069,11 +1093,16 @@ bool gconv_direct(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
 }
 
 int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, const Batch& bt, rn_stream_t stream,
-                  const Scratch& sc, const StatReq& sr) {
+                  const Scratch& sc, const StatReq& sr, const PlanOut& po) {
   if (int e = validate_geom(segs, nseg, g)) return e;
+  rn_conv_plan_call pc = {};                  // the decision: filled below, launched from
+  pc.nsplit = 1; pc.batched = bt.n; pc.grouped = ngroups(g) > 1;
   if (!sr.rows && !sr.bytes_out && gconv_direct(segs, nseg, g, bt, segs[0].bias != nullptr)) {
     if (sc.need_out) { *sc.need_out = 0; return RN_OK; }
     RN_CHECK_ARG(segs[0].x && segs[0].wgt && segs[0].y, "conv fwd: null pointer in segment 0");
+    pc.path = RN_CONV_PATH_DIRECT_GROUPED;
+    report(po, pc);
+    if (po.dry) return RN_OK;
     return rn::launch_gconv3x3(segs[0].x, segs[0].wgt, segs[0].y, segs[0].n, segs[0].h, segs[0].w, g->cin, ngroups(g), 0, (hipStream_t)stream);
   }
   RN_CHECK_ARG(bt.n == 1 || nseg == 1, "conv: batched mode takes one segment");
@@ -1102,10 +1131,13 @@ int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
         !d.bias && d.x_ld == 3 && d.x_coff == 0 && d.ow % STEM_RUN == 0 && (d.oh * d.ow) % STEM_PPB == 0 && (long)d.m * 32 < (1l << 31)) {
       const int ohw = d.oh * d.ow;
       if (sc.need_out) { *sc.need_out = 0; return RN_OK; }
+      pc.path = RN_CONV_PATH_STEM; pc.blocks = d.m / STEM_PPB;
       float2* rows = nullptr;
       if (sr.rows || sr.bytes_out) {
         const int groups = sr.rows ? sr.rows->groups : sr.groups;
         const bool ok = groups >= 1 && 32 % groups == 0 && rn_group_norm_rows_ok(32, groups, ohw / STEM_PPB, 0);
+        if (ok) pc.rows_per_sample = ohw / STEM_PPB;
+        report(po, pc);
         if (sr.bytes_out) {
           *sr.bytes_out = ok ? (size_t)(d.m / STEM_PPB) * 32 * 8 : 0;
           if (ok && sr.layout_out) { sr.layout_out->rows_per_sample = ohw / STEM_PPB; sr.layout_out->per_group = 0; sr.layout_out->groups = groups; }
@@ -1116,8 +1148,10 @@ int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
         RN_CHECK_ARG(sr.rows->rows, "conv fwd stats: null rows");
         rows = (float2*)sr.rows->rows;
       }
+      report(po, pc);
+      if (po.dry) return RN_OK;
       StemArgs st_a = {d.a, d.b, d.out, rows, d.n, d.h, d.w, d.oh, d.ow, d.pad_t, d.pad_l};
-      hipLaunchKernelGGL(stem_conv_fwd_kernel, dim3((unsigned)(d.m / STEM_PPB)), dim3(256), 0, (hipStream_t)stream, st_a);
+      hipLaunchKernelGGL(stem_conv_fwd_kernel, dim3((unsigned)pc.blocks), dim3(256), 0, (hipStream_t)stream, st_a);
       RN_LAUNCH_CHECK();
       return RN_OK;
     }
@@ -1138,10 +1172,16 @@ int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
     const int ohw = d.oh * d.ow;
     bool take = true;
     float2* rows = nullptr;
+    auto decide_x3 = [&]() { pc.path = colb ? RN_CONV_PATH_X3_PATCH : RN_CONV_PATH_X3_1X1; pc.m_tile = xrows; pc.n_piece = colb ? n_piece : 0; pc.patch_bytes = (int64_t)colb; };
     if (sr.rows || sr.bytes_out) {
       const int groups = sr.rows ? sr.rows->groups : sr.groups;
       const bool ok = ohw % xrows == 0 && groups >= 1 && d.cout % groups == 0 && (double)ohw * (d.cout / groups) < 16777216.0 &&
                       rn_group_norm_rows_ok(d.cout, groups, ohw / xrows, 0);
+      if (ok) {
+        decide_x3();
+        pc.rows_per_sample = ohw / xrows;
+        report(po, pc);
+      }
       if (!ok) {
         take = false;                       // (the fp32 kernels' tiles may still fit the map: fall through)
       } else if (sr.bytes_out) {
@@ -1157,6 +1197,9 @@ int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
     }
     if (take) {
       if (sc.need_out) { *sc.need_out = colb; return RN_OK; }
+      decide_x3();
+      report(po, pc);
+      if (po.dry) return RN_OK;
       if (!colb) return rn::launch_conv1x1_fwd_x3(d.a + d.x_coff, d.x_ld, d.b, d.out, d.m, g->cin, d.cout, rows, (hipStream_t)stream);
       const int K = g->kh * g->kw * g->cin;                    // W in HWIO is the [K][cout] matrix
       const int mp = n_piece * ohw;                            // rows of a piece (a whole number of m-tiles when rows are asked for)
@@ -1201,8 +1244,9 @@ int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
     a.seg[0].out = (float*)sc.ws;
     tiles *= nsplit;
   } else {
-    nsplit = 1;
+    nsplit = 1; ksplit = 0;
   }
+  pc.path = RN_CONV_PATH_FP32; pc.cfg = c; pc.load = load_variant(vec, tapu); pc.nsplit = nsplit; pc.ksplit = ksplit; pc.blocks = tiles;
   if (sr.rows || sr.bytes_out) {
     // rows ride on the plain single-segment kernel only, and the tile rows of a sample must be whole m-tiles
     const SegDev& d = a.seg[0];
@@ -1211,6 +1255,8 @@ int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
     const bool ok = nseg == 1 && bt.n == 1 && G == 1 && nsplit == 1 && !d.bias && ohw % bm == 0 && groups >= 1 && d.cout % groups == 0 &&
                     (double)ohw * (d.cout / groups) < 16777216.0 &&
                     rn_group_norm_rows_ok(d.cout, groups, ohw / bm, 0);
+    if (ok) pc.rows_per_sample = ohw / bm;
+    report(po, pc);
     if (sr.bytes_out) {
       *sr.bytes_out = ok ? (size_t)(d.m / bm) * d.cout * 8 : 0;
       if (ok && sr.layout_out) { sr.layout_out->rows_per_sample = ohw / bm; sr.layout_out->per_group = 0; sr.layout_out->groups = groups; }
@@ -1224,13 +1270,16 @@ int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
   static const int fpad_env = getenv("RN_PROD_LDS_PAD_FWD") ? atoi(getenv("RN_PROD_LDS_PAD_FWD")) : 0;
   static const int fpad_only_m = getenv("RN_PROD_LDS_PAD_FWD_ONLY_M") ? atoi(getenv("RN_PROD_LDS_PAD_FWD_ONLY_M")) : 0;   // (probe: only products of this many rows)
   const int fpad = (bt.n > 1 && (!fpad_only_m || a.seg[0].m == fpad_only_m)) ? fpad_env : 0;      // (batched = the Winograd products; see RN_PROD_LDS_PAD_BWD)
+  report(po, pc);
+  if (po.dry) return RN_OK;
+  const dim3 grid((unsigned)pc.blocks);
 #define RN_FWD(BM_, BN_, WM_, WN_)                                                                   \
   do {                                                                                               \
-    if (tapu) hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, WM_, WN_, 4, true>), dim3(tiles), dim3(WM_* WN_ * 64), fpad, st, a); \
-    else if (vec) hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, WM_, WN_, 4, false>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
-    else hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, WM_, WN_, 1, false>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a);     \
+    if (pc.load == RN_CONV_LOAD_VEC4_TAP) hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, WM_, WN_, 4, true>), grid, dim3(WM_* WN_ * 64), fpad, st, a); \
+    else if (pc.load == RN_CONV_LOAD_VEC4) hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, WM_, WN_, 4, false>), grid, dim3(WM_* WN_ * 64), 0, st, a); \
+    else hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, WM_, WN_, 1, false>), grid, dim3(WM_* WN_ * 64), 0, st, a);     \
   } while (0)
-  switch (c) {
+  switch (pc.cfg) {
     case 0: RN_FWD(128, 128, 2, 2); break;
     case 1: RN_FWD(128, 64, 2, 2); break;
     case 2: RN_FWD(64, 64, 2, 2); break;
@@ -1238,17 +1287,19 @@ int conv_fwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, cons
   }
 #undef RN_FWD
   RN_LAUNCH_CHECK();
-  if (nsplit > 1) {
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)rn::ceil_div64(out_elems, reduce_cols_per_block(nsplit))), dim3(256), 0, st, (const float*)sc.ws,
-                       y_final, out_elems, nsplit, 0);
+  if (pc.nsplit > 1) {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)rn::ceil_div64(out_elems, reduce_cols_per_block(pc.nsplit))), dim3(256), 0, st, (const float*)sc.ws,
+                       y_final, out_elems, pc.nsplit, 0);
     RN_LAUNCH_CHECK();
   }
   return RN_OK;
 }
 
 int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, const Batch& bt, rn_stream_t stream,
-                    const Scratch& sc, Planned* plan) {
+                    const Scratch& sc, Planned* plan, const PlanOut& po) {
   if (int e = validate_geom(segs, nseg, g)) return e;
+  rn_conv_plan_call pc = {};                  // the decision: filled below, launched from
+  pc.nsplit = 1; pc.batched = bt.n; pc.grouped = ngroups(g) > 1;
   if (!plan) {
     if (const size_t colb = x3_im2col(segs, nseg, g, bt, false)) {
       if (sc.need_out) { *sc.need_out = colb; return RN_OK; }
@@ -1258,6 +1309,9 @@ int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, co
         rn::same_pad(segs[0].h, g->kh, g->stride, &oh, &pt);
         rn::same_pad(segs[0].w, g->kw, g->stride, &ow, &pl);
         const int M = segs[0].n * oh * ow, K = g->kh * g->kw * g->cin;
+        pc.path = RN_CONV_PATH_X3_PATCH; pc.patch_bytes = (int64_t)colb; pc.m_tile = rn::x3_tile_rows(M, K, 1);
+        report(po, pc);
+        if (po.dry) return RN_OK;
         // dcol [M][K] = dy [M][cout] W^T  (W [K][cout]: the product's [N = K][k = cout] operand), then the gather
         if (int e = rn::launch_conv1x1_dgrad_x3(segs[0].dy, segs[0].wgt, (float*)sc.ws, K, M, K, segs[0].cout, (hipStream_t)stream)) return e;
         return rn::launch_col2im((const float*)sc.ws, segs[0].dx, segs[0].n, segs[0].h, segs[0].w, g->cin, g->kh, g->kw, g->stride, (hipStream_t)stream);
@@ -1267,6 +1321,9 @@ int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, co
   if (!plan && gconv_direct(segs, nseg, g, bt, false)) {       // the same direct kernel on dy, the kernel rotated / transposed per group
     if (sc.need_out) { *sc.need_out = 0; return RN_OK; }
     RN_CHECK_ARG(segs[0].dy && segs[0].wgt && segs[0].dx, "conv dgrad: null pointer in segment 0");
+    pc.path = RN_CONV_PATH_DIRECT_GROUPED;
+    report(po, pc);
+    if (po.dry) return RN_OK;
     return rn::launch_gconv3x3(segs[0].dy, segs[0].wgt, segs[0].dx, segs[0].n, segs[0].h, segs[0].w, g->cin, ngroups(g), 1, (hipStream_t)stream);
   }
   RN_CHECK_ARG(bt.n == 1 || nseg == 1, "conv: batched mode takes one segment");
@@ -1290,6 +1347,9 @@ int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, co
   if (!plan && x3_conv1x1(segs, nseg, g, bt, a.seg[0].m, a.seg[0].x_ld, false)) {      // (a `plan` request = the merged kernel: see rn_conv2d_bwd)
     if (sc.need_out) { *sc.need_out = 0; return RN_OK; }
     const SegDev& d = a.seg[0];
+    pc.path = RN_CONV_PATH_X3_1X1; pc.m_tile = rn::x3_tile_rows(d.m, g->cin, 1);
+    report(po, pc);
+    if (po.dry) return RN_OK;
     return rn::launch_conv1x1_dgrad_x3(d.a, d.b, d.out + d.x_coff, d.x_ld, d.m, g->cin, d.cout, (hipStream_t)stream);
   }
   // stride 2: an input pixel only sees the taps of its own row / column parity -- the plain implicit GEMM multiplies
@@ -1312,7 +1372,7 @@ int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, co
           d.kh0 = (py + d.pad_t) & 1; d.kw0 = (px + d.pad_l) & 1;
           d.nkh = d.kh0 < g->kh ? (g->kh - d.kh0 + 1) / 2 : 0;
           d.nkw = d.kw0 < g->kw ? (g->kw - d.kw0 + 1) / 2 : 0;
-          if (d.nkh == 0 || d.nkw == 0) { d.nkh = 0; d.nkw = 1; }  // no taps: the phase is all zeros
+          if (d.nkh == 0 || d.nkw == 0) { d.nkh = 0; d.nkw = 1; ++pc.phases_no_taps; }  // no taps: the phase is all zeros
           d.m = d.n * d.hc * d.wc;
           a.seg[k++] = d;
         }
@@ -1320,6 +1380,7 @@ int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, co
     }
     nseg = k;
     a.nseg = k;
+    pc.phases = k;
   }
   const int cin_g = a.cin_g;
   const int c = (G > 1 && cin_g <= 64) ? cfg_for_group_width(cin_g)
@@ -1352,20 +1413,24 @@ int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, co
     a.seg[0].out = (float*)sc.ws;
     tiles *= nsplit;
   } else {
-    nsplit = 1;
+    nsplit = 1; ksplit = 0;
   }
+  pc.path = RN_CONV_PATH_FP32; pc.cfg = c; pc.load = load_variant(vec, tapu); pc.nsplit = nsplit; pc.ksplit = ksplit; pc.blocks = tiles;
+  report(po, pc);
   if (plan) {
     plan->a = a; plan->cfg = c; plan->blocks = tiles; plan->vec = vec; plan->tapu = tapu;
     plan->simple = nsplit == 1 && !a.seg[0].par && bt.n == 1;
     return RN_OK;
   }
+  if (po.dry) return RN_OK;
+  const dim3 grid((unsigned)pc.blocks);
 #define RN_DG(BM_, BN_, WM_, WN_)                                                                    \
   do {                                                                                               \
-    if (tapu) hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, WM_, WN_, 4, true>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
-    else if (vec) hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, WM_, WN_, 4, false>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
-    else hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, WM_, WN_, 1, false>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a);     \
+    if (pc.load == RN_CONV_LOAD_VEC4_TAP) hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, WM_, WN_, 4, true>), grid, dim3(WM_* WN_ * 64), 0, st, a); \
+    else if (pc.load == RN_CONV_LOAD_VEC4) hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, WM_, WN_, 4, false>), grid, dim3(WM_* WN_ * 64), 0, st, a); \
+    else hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, WM_, WN_, 1, false>), grid, dim3(WM_* WN_ * 64), 0, st, a);     \
   } while (0)
-  switch (c) {
+  switch (pc.cfg) {
     case 0: RN_DG(128, 128, 2, 2); break;
     case 1: RN_DG(128, 64, 2, 2); break;
     case 2: RN_DG(64, 64, 2, 2); break;
@@ -1373,9 +1438,9 @@ int conv_dgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, co
   }
 #undef RN_DG
   RN_LAUNCH_CHECK();
-  if (nsplit > 1) {
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)rn::ceil_div64(out_elems, reduce_cols_per_block(nsplit))), dim3(256), 0, st, (const float*)sc.ws,
-                       dx_final, out_elems, nsplit, 0);
+  if (pc.nsplit > 1) {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)rn::ceil_div64(out_elems, reduce_cols_per_block(pc.nsplit))), dim3(256), 0, st, (const float*)sc.ws,
+                       dx_final, out_elems, pc.nsplit, 0);
     RN_LAUNCH_CHECK();
   }
   return RN_OK;
@@ -1469,7 +1534,7 @@ extern "C" size_t rn_conv2d_wgrad_workspace(const rn_conv_seg* segs, int nseg, c
 namespace {
 int conv_wgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, float* dw, int accumulate, void* workspace,
                     size_t workspace_bytes, const Batch& bt, rn_stream_t stream, int* nsplit_out = nullptr,
-                    Planned* plan = nullptr);
+                    Planned* plan = nullptr, const PlanOut& po = kNoPlan);
 }
 extern "C" int rn_conv2d_wgrad(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, float* dw, int accumulate,
                                void* workspace, size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer) {
@@ -1503,16 +1568,23 @@ int rn::launch_batched_gemm_tn(const float* A, const float* B, float* C, int M, 
 
 namespace {
 int conv_wgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, float* dw, int accumulate, void* workspace,
-                    size_t workspace_bytes, const Batch& bt, rn_stream_t stream, int* nsplit_out, Planned* plan) {
+                    size_t workspace_bytes, const Batch& bt, rn_stream_t stream, int* nsplit_out, Planned* plan, const PlanOut& po) {
   if (int e = validate_geom(segs, nseg, g)) return e;
   RN_CHECK_ARG((dw || nsplit_out) && workspace, "conv wgrad: null dw/workspace");
   RN_CHECK_ARG(bt.n == 1 || nseg == 1, "conv: batched mode takes one segment");
+  rn_conv_plan_call pc = {};                  // the decision: filled below, launched from
+  pc.nsplit = 1; pc.batched = bt.n; pc.grouped = ngroups(g) > 1;
+  const int reduce_how = rn::reduce_deferred((hipStream_t)stream) ? RN_CONV_REDUCE_DEFERRED : RN_CONV_REDUCE_LAUNCHED;
   if (!plan && !nsplit_out) {
     if (const size_t colb = x3_im2col(segs, nseg, g, bt, false)) {
       const int K = g->kh * g->kw * g->cin, M = (int)(colb / 4 / (size_t)K);
       const size_t slabs = rn::conv1x1_wgrad_workspace_x3(M, K, segs[0].cout);
       if (workspace_bytes >= colb + slabs) {
         RN_CHECK_ARG(segs[0].x && segs[0].dy && dw, "conv wgrad: null pointer in segment 0");
+        pc.path = RN_CONV_PATH_X3_PATCH; pc.patch_bytes = (int64_t)colb; pc.reduce = reduce_how;
+        rn::conv1x1_wgrad_split_x3(M, K, segs[0].cout, &pc.nsplit, &pc.ksplit, &pc.m_tile);
+        report(po, pc);
+        if (po.dry) return RN_OK;
         float* col = (float*)workspace;
         if (int e = rn::launch_im2col(segs[0].x, col, segs[0].n, segs[0].h, segs[0].w, g->cin, g->kh, g->kw, g->stride, (hipStream_t)stream)) return e;
         int ns = 0;
@@ -1524,6 +1596,9 @@ int conv_wgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, fl
   }
   if (!plan && !nsplit_out && gconv_direct(segs, nseg, g, bt, false)) {
     RN_CHECK_ARG(segs[0].x && segs[0].dy && dw, "conv wgrad: null pointer in segment 0");
+    pc.path = RN_CONV_PATH_DIRECT_GROUPED; pc.reduce = reduce_how;
+    report(po, pc);
+    if (po.dry) return dry_workspace_status(workspace_bytes, rn::gconv3x3_wgrad_workspace(segs[0].n, segs[0].h, segs[0].w, g->cin, ngroups(g)));
     return rn::launch_gconv3x3_wgrad(segs[0].x, segs[0].dy, dw, accumulate, segs[0].n, segs[0].h, segs[0].w, g->cin, ngroups(g), workspace,
                                      workspace_bytes, (hipStream_t)stream);
   }
@@ -1533,6 +1608,10 @@ int conv_wgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, fl
     const long m = (long)segs[0].n * segs[0].h * segs[0].w;
     if (x3_conv1x1(segs, nseg, g, bt, m, v.x_ld, false)) {
       RN_CHECK_ARG(segs[0].x && segs[0].dy, "conv wgrad: null pointer in segment 0");
+      pc.path = RN_CONV_PATH_X3_1X1; pc.reduce = reduce_how;
+      rn::conv1x1_wgrad_split_x3((int)m, g->cin, segs[0].cout, &pc.nsplit, &pc.ksplit, &pc.m_tile);
+      report(po, pc);
+      if (po.dry) return dry_workspace_status(workspace_bytes, rn::conv1x1_wgrad_workspace_x3((int)m, g->cin, segs[0].cout));
       int ns = 0;
       if (int e = rn::launch_conv1x1_wgrad_x3(segs[0].x + v.x_coff, v.x_ld, segs[0].dy, (int)m, g->cin, segs[0].cout, workspace, workspace_bytes,
                                               (hipStream_t)stream, &ns))
@@ -1566,17 +1645,23 @@ int conv_wgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, fl
   const bool vec = (a.cin_g % 4 == 0) && ((p.cout / a.groups) % 4 == 0);
   const int blocks = p.nsplit * bt.n * a.tiles_mn;
   hipStream_t st = (hipStream_t)stream;
+  pc.path = RN_CONV_PATH_FP32; pc.cfg = p.cfg; pc.load = load_variant(vec, false); pc.nsplit = p.nsplit; pc.ksplit = p.chunk[0]; pc.blocks = blocks;
+  for (int s = 0; s < nseg; ++s) pc.windows |= (p.pixels[s] < p.chunk[s] ? p.pixels[s] : p.chunk[s]) > WG_MAXPIX;
+  pc.direct = direct; pc.reduce = (direct || nsplit_out) ? RN_CONV_REDUCE_NONE : reduce_how;
+  report(po, pc);
   if (plan) {
     plan->a = a; plan->cfg = p.cfg; plan->blocks = blocks; plan->vec = vec; plan->tapu = false; plan->simple = bt.n == 1;
     plan->nsplit = p.nsplit; plan->direct = direct; plan->count = (int64_t)p.ktotal * p.cout;
     return RN_OK;
   }
+  if (po.dry) return RN_OK;
+  const dim3 grid((unsigned)pc.blocks);
 #define RN_WG(BM_, BN_, WM_, WN_)                                                                    \
   do {                                                                                               \
-    if (vec) hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, WM_, WN_, 4>), dim3(blocks), dim3(WM_* WN_ * 64), 0, st, a); \
-    else hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, WM_, WN_, 1>), dim3(blocks), dim3(WM_* WN_ * 64), 0, st, a);     \
+    if (pc.load != RN_CONV_LOAD_SCALAR) hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, WM_, WN_, 4>), grid, dim3(WM_* WN_ * 64), 0, st, a); \
+    else hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, WM_, WN_, 1>), grid, dim3(WM_* WN_ * 64), 0, st, a);     \
   } while (0)
-  switch (p.cfg) {
+  switch (pc.cfg) {
     case 0: RN_WG(128, 128, 2, 2); break;
     case 1: RN_WG(128, 64, 2, 2); break;
     case 2: RN_WG(64, 64, 2, 2); break;
@@ -1588,8 +1673,8 @@ int conv_wgrad_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, fl
     *nsplit_out = p.nsplit;
     return RN_OK;
   }
-  if (direct) return RN_OK;
-  return rn::launch_reduce_rows((const float*)workspace, dw, (int64_t)bt.n * p.ktotal * p.cout, p.nsplit, accumulate, st);
+  if (pc.direct) return RN_OK;
+  return rn::launch_reduce_rows((const float*)workspace, dw, (int64_t)bt.n * p.ktotal * p.cout, pc.nsplit, accumulate, st);
 }
 }  // namespace
 
@@ -1607,35 +1692,43 @@ ConvArgs4 compact(const ConvArgs& a) {
 // dx (segments' dx) and dw of one convolution.  Small problems (<= 4 segments, the 64x64 dgrad tile, no split-K / phase
 // decomposition) run as ONE launch of conv_bwd_kernel; everything else as rn_conv2d_dgrad followed by rn_conv2d_wgrad.
 // workspace: rn_conv2d_wgrad_workspace bytes.
-extern "C" int rn_conv2d_bwd(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, float* dw, void* workspace,
-                             size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer) {
-  rn::DeferScope defer_scope_(defer);
+namespace {
+// rn_conv2d_bwd; `plan` (rn_conv2d_plan): the decision, `dry`: no launch
+int conv_bwd_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, float* dw, void* workspace, size_t workspace_bytes,
+                  rn_stream_t stream, rn_conv_plan* plan, bool dry) {
   static const bool enabled = getenv("RN_NO_MERGED_BWD") == nullptr;
   Planned pd, pw;
-  bool merge = enabled && nseg <= 4;
-  if (merge && nseg == 1 && validate_geom(segs, nseg, g) == 0) {      // dense 1x1 in product mode 1: two split-bf16 launches instead
+  rn_conv_plan bp = {};                       // the decision: filled below, launched from
+  bp.unmerged = !enabled ? RN_CONV_UNMERGED_SWITCH : (nseg > 4 ? RN_CONV_UNMERGED_SHAPE : RN_CONV_MERGED);
+  if (!bp.unmerged && nseg == 1 && validate_geom(segs, nseg, g) == 0) {      // dense 1x1 in product mode 1: two split-bf16 launches instead
     SegDev v = {};
     set_x_view(v, segs[0], g->cin);
-    if (x3_conv1x1(segs, nseg, g, Batch{1, 0, 0, 0}, (long)segs[0].n * segs[0].h * segs[0].w, v.x_ld, false)) merge = false;
-    if (gconv_direct(segs, nseg, g, Batch{1, 0, 0, 0}, false)) merge = false;          // ... grouped 3x3: the direct kernels
-    if (x3_im2col(segs, nseg, g, Batch{1, 0, 0, 0}, false)) merge = false;             // ... dense k x k / stride 2: patch matrix + split products
+    if (x3_im2col(segs, nseg, g, Batch{1, 0, 0, 0}, false)) bp.unmerged = RN_CONV_UNMERGED_PATCH;     // dense k x k / stride 2: patch matrix + split products
+    if (gconv_direct(segs, nseg, g, Batch{1, 0, 0, 0}, false)) bp.unmerged = RN_CONV_UNMERGED_DIRECT;   // ... grouped 3x3: the direct kernels
+    if (x3_conv1x1(segs, nseg, g, Batch{1, 0, 0, 0}, (long)segs[0].n * segs[0].h * segs[0].w, v.x_ld, false)) bp.unmerged = RN_CONV_UNMERGED_X3_1X1;
   }
-  if (merge) {
-    if (int e = conv_dgrad_impl(segs, nseg, g, Batch{1, 0, 0, 0}, stream, Scratch{nullptr, 0, nullptr}, &pd)) return e;
-    if (int e = conv_wgrad_impl(segs, nseg, g, dw, 0, workspace, workspace_bytes, Batch{1, 0, 0, 0}, stream, nullptr, &pw)) return e;
-    merge = pd.simple && pd.vec && pw.vec && pd.cfg == 2 && pd.a.nseg <= 4 && pw.a.nseg <= 4;
+  if (!bp.unmerged) {
+    if (int e = conv_dgrad_impl(segs, nseg, g, Batch{1, 0, 0, 0}, stream, Scratch{nullptr, 0, nullptr}, &pd, PlanOut{&bp.dgrad, true})) return e;
+    if (int e = conv_wgrad_impl(segs, nseg, g, dw, 0, workspace, workspace_bytes, Batch{1, 0, 0, 0}, stream, nullptr, &pw, PlanOut{&bp.wgrad, true})) return e;
+    if (!(pd.simple && pd.vec && pw.vec && pd.cfg == 2 && pd.a.nseg <= 4 && pw.a.nseg <= 4)) bp.unmerged = RN_CONV_UNMERGED_SHAPE;
   }
-  if (!merge) {
+  if (bp.unmerged) {
     // (the patch-matrix path of the data gradient needs the scratch -- the weight gradient's is at least as large; every other
     // shape keeps the scratch-free data gradient it always had)
     const bool ic = nseg == 1 && validate_geom(segs, nseg, g) == 0 && x3_im2col(segs, nseg, g, Batch{1, 0, 0, 0}, false) != 0;
-    if (int e = conv_dgrad_impl(segs, nseg, g, Batch{1, 0, 0, 0}, stream, ic ? Scratch{workspace, workspace_bytes, nullptr} : Scratch{nullptr, 0, nullptr}))
-      return e;
-    return conv_wgrad_impl(segs, nseg, g, dw, 0, workspace, workspace_bytes, Batch{1, 0, 0, 0}, stream);
+    const PlanOut pod = {&bp.dgrad, dry}, pow_ = {&bp.wgrad, dry};
+    bp.dgrad = rn_conv_plan_call{}; bp.wgrad = rn_conv_plan_call{};
+    int e = conv_dgrad_impl(segs, nseg, g, Batch{1, 0, 0, 0}, stream, ic ? Scratch{workspace, workspace_bytes, nullptr} : Scratch{nullptr, 0, nullptr}, nullptr, pod);
+    if (!e) e = conv_wgrad_impl(segs, nseg, g, dw, 0, workspace, workspace_bytes, Batch{1, 0, 0, 0}, stream, nullptr, nullptr, pow_);
+    if (plan) *plan = bp;
+    return e;
   }
+  bp.call.path = RN_CONV_PATH_MERGED_BWD; bp.call.blocks = pd.blocks + pw.blocks; bp.call.nsplit = 1; bp.call.batched = 1;
+  if (plan) *plan = bp;
+  if (dry) return RN_OK;
   const ConvArgs4 d4 = compact(pd.a), w4 = compact(pw.a);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(pd.blocks + pw.blocks));
+  const dim3 grid((unsigned)bp.call.blocks);
 #define RN_BWD(WBM_, WBN_, WWM_, WWN_)                                                                                          \
   do {                                                                                                                          \
     if (pd.tapu) hipLaunchKernelGGL((conv_bwd_kernel<64, 64, 2, 2, true, WBM_, WBN_, WWM_, WWN_>), grid, dim3(256), 0, st, d4, w4, pd.blocks); \
@@ -1651,6 +1744,48 @@ extern "C" int rn_conv2d_bwd(const rn_conv_seg* segs, int nseg, const rn_conv_ge
   RN_LAUNCH_CHECK();
   if (pw.direct) return RN_OK;
   return rn::launch_reduce_rows((const float*)workspace, dw, pw.count, pw.nsplit, 0, st);
+}
+}  // namespace
+extern "C" int rn_conv2d_bwd(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, float* dw, void* workspace,
+                             size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer) {
+  rn::DeferScope defer_scope_(defer);
+  return conv_bwd_impl(segs, nseg, g, dw, workspace, workspace_bytes, stream, nullptr, false);
+}
+
+// ---------------------------------------------------------------------------------------------
+// rn_conv2d_plan: the entry points' own decision functions, stopped before the first launch
+// ---------------------------------------------------------------------------------------------
+extern "C" int rn_conv2d_plan(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int op, int stats_groups, int accumulate, int defer,
+                              const float* dw, const void* workspace, size_t workspace_bytes, rn_conv_plan* plan) {
+  RN_CHECK_ARG(plan, "conv plan: null plan");
+  *plan = rn_conv_plan{};
+  rn_reduce_list none = {};                   // (stands for the caller's list: nothing is recorded in a dry run)
+  rn::DeferScope defer_scope_(defer ? &none : nullptr);
+  const Batch one = {1, 0, 0, 0};
+  const Scratch sc = {(void*)workspace, workspace_bytes, nullptr};
+  const PlanOut po = {&plan->call, true};
+  switch (op) {
+    case RN_CONV_FWD: return conv_fwd_impl(segs, nseg, g, one, nullptr, sc, StatReq{nullptr, 0, nullptr, nullptr}, po);
+    case RN_CONV_FWD_STATS: {
+      size_t bytes = 0;
+      if (int e = conv_fwd_impl(segs, nseg, g, one, nullptr, sc, StatReq{nullptr, stats_groups, nullptr, &bytes}, po)) return e;
+      RN_UNSUPPORTED(!bytes, "conv fwd stats: this shape / layout cannot produce GroupNorm rows (rn_conv2d_stats_rows)");
+      return RN_OK;
+    }
+    case RN_CONV_DGRAD: return conv_dgrad_impl(segs, nseg, g, one, nullptr, sc, nullptr, po);
+    case RN_CONV_WGRAD: return conv_wgrad_impl(segs, nseg, g, (float*)dw, accumulate, (void*)workspace, workspace_bytes, one, nullptr, nullptr, nullptr, po);
+    case RN_CONV_BWD: return conv_bwd_impl(segs, nseg, g, (float*)dw, (void*)workspace, workspace_bytes, nullptr, plan, true);
+    default: break;
+  }
+  rn::set_error("conv plan: unknown op %d", op);
+  return RN_EINVAL;
+}
+extern "C" int rn_gemm_batched_plan(const float* A, const float* B, const float* C, int M, int K, int N, int nbatch, int b_nk, rn_conv_plan* plan) {
+  RN_CHECK_ARG(plan, "gemm plan: null plan");
+  *plan = rn_conv_plan{};
+  RN_CHECK_ARG(A && B && C && M >= 1 && K >= 1 && N >= 1 && nbatch >= 1, "gemm_batched: bad argument");        // (rn_gemm_batched's own checks)
+  RN_UNSUPPORTED(K % 4 != 0 || N % 4 != 0, "gemm_batched: K %d / N %d must be multiples of 4", K, N);
+  return batched_gemm_impl(A, B, (float*)C, M, K, N, nbatch, b_nk, nullptr, PlanOut{&plan->call, true});
 }
 
 // The two batched products of a Winograd backward pass in ONE launch (same trick as rn_conv2d_bwd):

@@ -315,6 +315,8 @@ int launch_conv1x1_dgrad_x3(const float* dy, const float* w, float* dx, int dx_l
   return launch(a, false, false, tile_rows(M, Cin, 1), st);
 }
 size_t conv1x1_wgrad_workspace_x3(int M, int Cin, int Cout) { return batched_gemm_tn_workspace_x3(M, Cin, Cout, 1); }
+// what launch_conv1x1_wgrad_x3 launches (rn_conv2d_plan): slabs, pixels per slab, tile rows
+void conv1x1_wgrad_split_x3(int M, int Cin, int Cout, int* nsplit, int* chunk, int* rows) { tn_split(M, Cin, Cout, 1, nsplit, chunk, rows); }
 // slabs [nsplit][Cin][Cout] of x^T dy in `workspace` (the caller sums them: rn::launch_reduce_rows)
 int launch_conv1x1_wgrad_x3(const float* x, int x_ld, const float* dy, int M, int Cin, int Cout, void* workspace, size_t workspace_bytes,
                             hipStream_t st, int* nsplit_out) {

@@ -73,6 +73,7 @@ int launch_conv1x1_fwd_x3(const float* x, int x_ld, const float* w, float* y, in
                           float drop_rate = 0.f, uint64_t drop_seed = 0, const uint64_t* drop_seed_dev = nullptr);
 int launch_conv1x1_dgrad_x3(const float* dy, const float* w, float* dx, int dx_ld, int M, int Cin, int Cout, hipStream_t st);
 size_t conv1x1_wgrad_workspace_x3(int M, int Cin, int Cout);
+void conv1x1_wgrad_split_x3(int M, int Cin, int Cout, int* nsplit, int* chunk, int* rows);
 int launch_conv1x1_wgrad_x3(const float* x, int x_ld, const float* dy, int M, int Cin, int Cout, void* workspace, size_t workspace_bytes,
                             hipStream_t st, int* nsplit_out);
 // dense k x k convs (not 1 x 1 / stride 1) as split-bf16 products of an explicit patch matrix (im2col.hip); bytes == 0: not taken
