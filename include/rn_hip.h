@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 421
+#define RN_API_VERSION 422
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -1112,6 +1112,40 @@ int rn_nms_classwise(const float* boxes, const float* scores, const int32_t* cla
                      const int64_t* count_dev, const rn_det_params* p, float* out_boxes, float* out_scores,
                      int32_t* out_class, int32_t* out_image, int64_t* out_index, int64_t* counts, void* workspace,
                      size_t workspace_bytes, rn_stream_t stream);
+
+/* Which kernels one rn_detect / rn_boxes_decode call with these levels and parameters launches, and with which grids -- for
+ * tests that must know which implementation a shape takes.  It is the decision the entry points themselves run before they
+ * launch (one function: the same constants, RN_SCAN_LDS / RN_SCAN_NO_LDS read at the call, RN_SCAN_T / RN_SCAN_NT read once
+ * per process).  Host only: touches no device, launches nothing; of the levels only rows_per_image, prob_f16 and
+ * prob_is_logit decide (data pointers may be NULL).  nlevels == 0 (levels ignored): the plan of rn_nms_classwise, which runs
+ * no scan, offsets or emit pass (scan == RN_DET_SCAN_NONE, their fields 0).  Returns what the launch would return for the
+ * same shapes (RN_EINVAL / RN_EUNSUPPORTED), RN_EINVAL for a NULL plan. */
+enum rn_det_scan {
+  RN_DET_SCAN_NONE = 0,
+  RN_DET_SCAN_T = 1,       /* det_scan_t_kernel: fp16 maps of 80 classes, transposed through LDS, non-temporal loads */
+  RN_DET_SCAN_T_PLAIN = 2, /* the same with plain loads (RN_SCAN_NT=0)                                                */
+  RN_DET_SCAN_Q = 3,       /* det_scan_q_kernel<scan_half, scan_logit, scan_q>: four lanes per row, q chunks per lane */
+  RN_DET_SCAN_LDS = 4,     /* det_scan_lds_kernel (RN_SCAN_LDS): rows staged through scan_lds_per_wave bytes per wave  */
+  RN_DET_SCAN_GENERIC = 5  /* det_scan_kernel: any class count, levels of mixed storage type / logit flag             */
+};
+enum rn_det_emit { RN_DET_EMIT_NONE = 0, RN_DET_EMIT_HIST = 1, RN_DET_EMIT_STRIDED = 2 };
+enum rn_det_segments {
+  RN_DET_SEG_LDS_SCATTER = 1,   /* det_seg_scatter_kernel: the segment scan in every block's LDS               */
+  RN_DET_SEG_GLOBAL_SCATTER = 2 /* det_seg_scan_kernel + det_seg_scatter_global_kernel (more than 8192 segments) */
+};
+typedef struct rn_det_plan {
+  int32_t scan;                             /* rn_det_scan */
+  int32_t scan_half, scan_logit, scan_q;    /* RN_DET_SCAN_Q: the kernel's template arguments; else 0 */
+  int32_t scan_lds_per_wave;                /* RN_DET_SCAN_LDS: bytes per wave; else 0 */
+  int32_t scan_grid;                        /* blocks of the scan kernel */
+  int32_t offsets_blocks;                   /* blocks of det_offsets_kernel */
+  int32_t emit_mode, emit_grid;             /* rn_det_emit, blocks of det_emit_kernel */
+  int32_t emit_lds_bytes;                   /* its dynamic LDS */
+  int32_t segments;                         /* rn_det_segments (rn_boxes_decode stops before it) */
+  int32_t nseg;                             /* n * num_classes: blocks of the sort, NMS and gather kernels */
+  uint64_t workspace_bytes;                 /* = rn_detect_workspace / rn_nms_classwise_workspace */
+} rn_det_plan;
+int rn_detect_plan(const rn_det_level* levels, int nlevels, const rn_det_params* p, rn_det_plan* plan);
 
 /* ------------------------------------------------------------------ optimizer
  * Replaces tf.train.{Momentum,RMSProp,Adam}Optimizer.apply + the L2 regulariser gradient

@@ -22,7 +22,7 @@ LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
 CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
-API_VERSION = 421        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 422        # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -265,6 +265,20 @@ class DetParams(C.Structure):
                 ("score_threshold", C.c_float), ("iou_threshold", C.c_float), ("max_candidates", C.c_int64)]
 
 
+class DetPlan(C.Structure):
+    """rn_det_plan: the kernels one rn_detect / rn_boxes_decode / rn_nms_classwise call launches (rn_detect_plan, host only)"""
+    _fields_ = [("scan", C.c_int32), ("scan_half", C.c_int32), ("scan_logit", C.c_int32), ("scan_q", C.c_int32),
+                ("scan_lds_per_wave", C.c_int32), ("scan_grid", C.c_int32), ("offsets_blocks", C.c_int32),
+                ("emit_mode", C.c_int32), ("emit_grid", C.c_int32), ("emit_lds_bytes", C.c_int32),
+                ("segments", C.c_int32), ("nseg", C.c_int32), ("workspace_bytes", C.c_uint64)]
+
+
+# enum rn_det_scan / rn_det_emit / rn_det_segments
+DET_SCANS = {0: None, 1: "T", 2: "T_PLAIN", 3: "Q", 4: "LDS", 5: "GENERIC"}
+DET_EMITS = {0: None, 1: "HIST", 2: "STRIDED"}
+DET_SEGMENTS = {1: "LDS_SCATTER", 2: "GLOBAL_SCATTER"}
+
+
 _lib = None
 
 # every symbol include/rn_hip.h declares (tests/test_abi.py checks the .so exports them all)
@@ -287,7 +301,7 @@ SYMBOLS = [
     "rn_loss_workspace", "rn_loss_fwd", "rn_loss_bwd",
     "rn_loss_terms_stats_floats", "rn_loss_terms_workspace", "rn_loss_terms_fwd", "rn_loss_terms_bwd",
     "rn_iou", "rn_anchor_assign", "rn_anchor_assign_levels", "rn_anchor_assign_levels_pair", "rn_decode_boxes", "rn_detect_workspace", "rn_detect",
-    "rn_boxes_decode", "rn_nms_classwise_workspace", "rn_nms_classwise",
+    "rn_boxes_decode", "rn_nms_classwise_workspace", "rn_nms_classwise", "rn_detect_plan",
     "rn_optimizer_workspace", "rn_grad_norm_l2reg", "rn_optimizer_update", "rn_counter_add", "rn_add_segs",
     "rn_mb_rows_max", "rn_mb_compact_rows_layout", "rn_mb_compact_rows", "rn_mb_pointwise_rows", "rn_mb_pointwise_fwd", "rn_mb_depthwise_rows", "rn_mb_depthwise_fwd", "rn_mb_apply",
     "rn_mb_resident_sync_bytes", "rn_mb_resident_rows", "rn_mb_resident_fwd", "rn_set_product_mode", "rn_get_product_mode",
@@ -468,6 +482,7 @@ def lib():
                                                                                      C.c_void_p]
         L.rn_boxes_decode.argtypes = L.rn_detect.argtypes
         L.rn_nms_classwise_workspace.argtypes = [C.c_void_p]
+        L.rn_detect_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DetPlan)]
         L.rn_nms_classwise.argtypes = [C.c_void_p] * 5 + [C.c_void_p] + [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t,
                                                                                         C.c_void_p]
         L.rn_grad_norm_l2reg.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_float, C.c_void_p, C.c_void_p,

@@ -617,9 +617,11 @@ __global__ __launch_bounds__(T) void det_emit_kernel(const DetArgs a) {
   }
 }
 
-// order-preserving map of ANY float onto unsigned integers (scores handed to rn_nms_classwise may be <= 0)
+// order-preserving map of ANY float onto unsigned integers (scores handed to rn_nms_classwise may be <= 0).  -0.0 and +0.0
+// compare equal (the reference's comparator, a stable argsort): both take +0.0's key, so the lower index decides between them
 __device__ __forceinline__ uint32_t float_order(float s) {
-  const uint32_t sb = __float_as_uint(s);
+  uint32_t sb = __float_as_uint(s);
+  if ((sb << 1) == 0u) sb = 0u;
   return (sb & 0x80000000u) ? ~sb : (sb | 0x80000000u);
 }
 
@@ -782,7 +784,10 @@ __device__ __forceinline__ bool suppresses(const NBox& i, const NBox& j, float t
 
 // The same decision without the division wherever it is safe: v = inter / u > thr  <=>  inter > thr u up to rounding; outside a
 // relative band of 2^-20 around equality the rounded quotient cannot land on the other side of thr (each of the roundings
-// involved is <= 2^-23 relative), inside it the exact expression decides.  Bit-identical to `suppresses`.
+// involved is <= 2^-23 relative), inside it the exact expression decides.  A subnormal thr u keeps that true for a normal thr
+// (inter and thr u are then whole denormal units: one unit apart is either inside the band or >= 2^-21 relative); a threshold
+// that is itself zero or subnormal does not (thr = 0, inter = 2^-149, u = 9: inter > 0 but inter / u == 0), so the exact
+// expression decides for it -- a wave-uniform test on a kernel argument, nothing added per pair.  Bit-identical to `suppresses`.
 __device__ __forceinline__ bool suppresses_fast(const NBox& i, const NBox& j, float thr) {
   const float iy = fmaxf(fminf(i.ymax, j.ymax) - fmaxf(i.ymin, j.ymin), 0.f);
   const float ix = fmaxf(fminf(i.xmax, j.xmax) - fmaxf(i.xmin, j.xmin), 0.f);
@@ -791,7 +796,7 @@ __device__ __forceinline__ bool suppresses_fast(const NBox& i, const NBox& j, fl
   const float t = thr * u;
   const bool valid = i.area > 0.f && j.area > 0.f;
   bool r = inter > t;
-  if (fabsf(inter - t) <= 9.5367431640625e-07f * fabsf(t)) r = (inter / u) > thr;      // (rare: wave-divergent exact path)
+  if (fabsf(inter - t) <= 9.5367431640625e-07f * fabsf(t) || thr < 1.17549435e-38f) r = (inter / u) > thr;      // (rare: wave-divergent exact path)
   return valid && r;
 }
 
@@ -1009,9 +1014,59 @@ __global__ void det_count_arrays_kernel(const DetArgs a, const int64_t* count_de
   if (blockIdx.x == 0 && threadIdx.x == 0) a.counts[0] = count_dev[0];
 }
 
-int sort_and_suppress(DetArgs& a, const WsLayout& L, void* workspace, hipStream_t st) {
-  const int nseg = a.n * a.C;
-  if (nseg <= SCAT_MAXSEG) {
+// ---- the host-side choices of one call: the scan kernel, the grids, the emit mode, the segment path.  run_detect and
+// sort_and_suppress launch what this says and rn_detect_plan reports it: the ONLY copy of these rules.
+void choose_segments(const DetArgs& a, const WsLayout& L, rn_det_plan* pl) {
+  memset(pl, 0, sizeof *pl);
+  pl->nseg = a.n * a.C;
+  pl->segments = pl->nseg <= SCAT_MAXSEG ? RN_DET_SEG_LDS_SCATTER : RN_DET_SEG_GLOBAL_SCATTER;
+  pl->workspace_bytes = L.total;
+}
+
+void choose(const DetArgs& a, const WsLayout& L, rn_det_plan* pl) {
+  choose_segments(a, L, pl);
+  const int64_t nw = (int64_t)a.n * a.waves_per_image;
+  const unsigned wblocks = (unsigned)((nw * 64 + T - 1) / T);
+  pl->scan_grid = (int32_t)wblocks;
+  // LDS-staged scan when every level's rows are whole 16-byte chunks and 64 of them (padded) fit a wave's LDS share
+  bool lds_ok = getenv("RN_SCAN_NO_LDS") == nullptr;
+  size_t need = 0;
+  for (int l = 0; l < a.nlv; ++l) {
+    const int esz = a.lv[l].half_prob ? 2 : 4, v = 16 / esz;
+    const size_t w = (size_t)64 * (((a.C / v) | 1) * 16);
+    lds_ok = lds_ok && a.C % v == 0 && w <= (size_t)SCAN_LDS_WAVE;
+    need = need > w ? need : w;
+  }
+  // all levels in one storage type / logit mode with whole 16-byte chunks: the kernel specialised for that case
+  bool uniform = true;
+  for (int l = 1; l < a.nlv; ++l) uniform = uniform && a.lv[l].half_prob == a.lv[0].half_prob && a.lv[l].logit == a.lv[0].logit;
+  const int v0 = a.lv[0].half_prob ? 8 : 4;
+  const int qpl = a.C % v0 == 0 ? (a.C / v0 + 3) / 4 : 0;
+  lds_ok = lds_ok && getenv("RN_SCAN_LDS") != nullptr;   // measured slower than the specialised kernels: opt-in only
+  // fp16 maps of 80 classes (cfg 5): the transposing scan; RN_SCAN_T=0: the four-lanes-per-row kernels
+  static const bool scan_t = !(getenv("RN_SCAN_T") && atoi(getenv("RN_SCAN_T")) == 0);
+  if (scan_t && uniform && a.lv[0].half_prob && a.C == 80 && !lds_ok) {
+    static const bool nt = !(getenv("RN_SCAN_NT") && atoi(getenv("RN_SCAN_NT")) == 0);   // (0: A/B measurements)
+    pl->scan = nt ? RN_DET_SCAN_T : RN_DET_SCAN_T_PLAIN;
+  } else if (uniform && qpl >= 1 && qpl <= 8 && !lds_ok) {
+    pl->scan = RN_DET_SCAN_Q;
+    pl->scan_half = a.lv[0].half_prob; pl->scan_logit = a.lv[0].logit; pl->scan_q = qpl;
+  } else if (lds_ok) {
+    pl->scan = RN_DET_SCAN_LDS;
+    pl->scan_lds_per_wave = (int32_t)need;
+  } else {
+    pl->scan = RN_DET_SCAN_GENERIC;
+  }
+  pl->offsets_blocks = (int32_t)((nw + 1023) / 1024);
+  const bool hist = pl->nseg <= EMIT_MAXSEG && a.cap * 8 >= (int64_t)a.n * a.rows_per_image;     // (the kernel's own rule)
+  pl->emit_mode = hist ? RN_DET_EMIT_HIST : RN_DET_EMIT_STRIDED;
+  pl->emit_grid = (int32_t)(wblocks < 2048u ? wblocks : 2048u);
+  pl->emit_lds_bytes = hist ? (int32_t)((size_t)pl->nseg * sizeof(int)) : 0;
+}
+
+int sort_and_suppress(DetArgs& a, const rn_det_plan& pl, hipStream_t st) {
+  const int nseg = pl.nseg;
+  if (pl.segments == RN_DET_SEG_LDS_SCATTER) {
     hipLaunchKernelGGL(det_seg_scatter_kernel, dim3(256), dim3(SCAT_T), 0, st, a);
   } else {
     hipLaunchKernelGGL(det_seg_scan_kernel, dim3(1), dim3(1024), 0, st, a);
@@ -1041,34 +1096,24 @@ int run_detect(const rn_det_level* levels, int nlevels, const rn_det_params* p, 
   a.out_boxes = out_boxes; a.out_scores = out_scores; a.out_class = out_class; a.out_image = out_image;
   a.out_anchor = out_anchor; a.counts = counts;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t nw = (int64_t)a.n * a.waves_per_image;
-  const unsigned wblocks = (unsigned)((nw * 64 + T - 1) / T);
-  {
-    // LDS-staged scan when every level's rows are whole 16-byte chunks and 64 of them (padded) fit a wave's LDS share
-    bool lds_ok = getenv("RN_SCAN_NO_LDS") == nullptr;
-    for (int l = 0; l < a.nlv; ++l) {
-      const int esz = a.lv[l].half_prob ? 2 : 4, v = 16 / esz;
-      lds_ok = lds_ok && a.C % v == 0 && 64 * (((a.C / v) | 1) * 16) <= SCAN_LDS_WAVE;
-    }
-    // all levels in one storage type / logit mode with whole 16-byte chunks: the kernel specialised for that case
-    bool uniform = true;
-    for (int l = 1; l < a.nlv; ++l) uniform = uniform && a.lv[l].half_prob == a.lv[0].half_prob && a.lv[l].logit == a.lv[0].logit;
-    const int v0 = a.lv[0].half_prob ? 8 : 4;
-    const int qpl = a.C % v0 == 0 ? (a.C / v0 + 3) / 4 : 0;
-    lds_ok = lds_ok && getenv("RN_SCAN_LDS") != nullptr;   // measured slower than the specialised kernels: opt-in only
-    // fp16 maps of 80 classes (cfg 5): the transposing scan; RN_SCAN_T=0: the four-lanes-per-row kernels
-    static const bool scan_t = !(getenv("RN_SCAN_T") && atoi(getenv("RN_SCAN_T")) == 0);
-    if (scan_t && uniform && a.lv[0].half_prob && a.C == 80 && !lds_ok) {
+  rn_det_plan pl;
+  choose(a, L, &pl);
+  const unsigned wblocks = (unsigned)pl.scan_grid;
+  const bool logit = a.lv[0].logit != 0;
+  switch (pl.scan) {
+    case RN_DET_SCAN_T:
+    case RN_DET_SCAN_T_PLAIN: {
       constexpr size_t tl = (size_t)(T / 64) * 32 * ((10 | 1) * 16);
-      static const bool nt = !(getenv("RN_SCAN_NT") && atoi(getenv("RN_SCAN_NT")) == 0);   // (0: A/B measurements)
-      if (!nt) {
-        if (a.lv[0].logit) hipLaunchKernelGGL((det_scan_t_kernel<10, true, false>), dim3(wblocks), dim3(T), tl, st, a);
+      if (pl.scan == RN_DET_SCAN_T_PLAIN) {
+        if (logit) hipLaunchKernelGGL((det_scan_t_kernel<10, true, false>), dim3(wblocks), dim3(T), tl, st, a);
         else hipLaunchKernelGGL((det_scan_t_kernel<10, false, false>), dim3(wblocks), dim3(T), tl, st, a);
-      } else if (a.lv[0].logit) hipLaunchKernelGGL((det_scan_t_kernel<10, true>), dim3(wblocks), dim3(T), tl, st, a);
+      } else if (logit) hipLaunchKernelGGL((det_scan_t_kernel<10, true>), dim3(wblocks), dim3(T), tl, st, a);
       else hipLaunchKernelGGL((det_scan_t_kernel<10, false>), dim3(wblocks), dim3(T), tl, st, a);
-    } else if (uniform && qpl >= 1 && qpl <= 8 && !lds_ok) {
+      break;
+    }
+    case RN_DET_SCAN_Q: {
 #define RN_SCAN_Q(H_, L_)                                                                                         \
-      switch (qpl) {                                                                                              \
+      switch (pl.scan_q) {                                                                                        \
         case 1: hipLaunchKernelGGL((det_scan_q_kernel<H_, L_, 1>), dim3(wblocks), dim3(T), 0, st, a); break;      \
         case 2: hipLaunchKernelGGL((det_scan_q_kernel<H_, L_, 2>), dim3(wblocks), dim3(T), 0, st, a); break;      \
         case 3: hipLaunchKernelGGL((det_scan_q_kernel<H_, L_, 3>), dim3(wblocks), dim3(T), 0, st, a); break;      \
@@ -1078,36 +1123,29 @@ int run_detect(const rn_det_level* levels, int nlevels, const rn_det_params* p, 
         case 7: hipLaunchKernelGGL((det_scan_q_kernel<H_, L_, 7>), dim3(wblocks), dim3(T), 0, st, a); break;      \
         default: hipLaunchKernelGGL((det_scan_q_kernel<H_, L_, 8>), dim3(wblocks), dim3(T), 0, st, a); break;     \
       }
-      if (a.lv[0].half_prob) { if (a.lv[0].logit) { RN_SCAN_Q(true, true) } else { RN_SCAN_Q(true, false) } }
-      else { if (a.lv[0].logit) { RN_SCAN_Q(false, true) } else { RN_SCAN_Q(false, false) } }
+      if (pl.scan_half) { if (logit) { RN_SCAN_Q(true, true) } else { RN_SCAN_Q(true, false) } }
+      else { if (logit) { RN_SCAN_Q(false, true) } else { RN_SCAN_Q(false, false) } }
 #undef RN_SCAN_Q
-    } else if (lds_ok) {
+      break;
+    }
+    case RN_DET_SCAN_LDS: {
       static const hipError_t attr_ = hipFuncSetAttribute((const void*)det_scan_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                           (T / 64) * SCAN_LDS_WAVE);
       (void)attr_;
-      size_t need = 0;
-      for (int l = 0; l < a.nlv; ++l) {
-        const int esz = a.lv[l].half_prob ? 2 : 4, v = 16 / esz;
-        const size_t w = (size_t)64 * (((a.C / v) | 1) * 16);
-        need = need > w ? need : w;
-      }
-      hipLaunchKernelGGL(det_scan_lds_kernel, dim3(wblocks), dim3(T), (size_t)(T / 64) * need, st, a, (int)need);
-    } else {
-      hipLaunchKernelGGL(det_scan_kernel, dim3(wblocks), dim3(T), 0, st, a);
+      hipLaunchKernelGGL(det_scan_lds_kernel, dim3(wblocks), dim3(T), (size_t)(T / 64) * pl.scan_lds_per_wave, st, a, pl.scan_lds_per_wave);
+      break;
     }
+    default:
+      hipLaunchKernelGGL(det_scan_kernel, dim3(wblocks), dim3(T), 0, st, a);
   }
-  hipLaunchKernelGGL(det_offsets_kernel, dim3((unsigned)((nw + 1023) / 1024)), dim3(1024), 0, st, a);
-  {
-    const int nseg_ = a.n * a.C;
-    const bool hist = nseg_ <= EMIT_MAXSEG && a.cap * 8 >= (int64_t)a.n * a.rows_per_image;     // (the kernel's own rule)
-    hipLaunchKernelGGL(det_emit_kernel, dim3(wblocks < 2048u ? wblocks : 2048u), dim3(T), hist ? (size_t)nseg_ * sizeof(int) : 0, st, a);
-  }
+  hipLaunchKernelGGL(det_offsets_kernel, dim3((unsigned)pl.offsets_blocks), dim3(1024), 0, st, a);
+  hipLaunchKernelGGL(det_emit_kernel, dim3((unsigned)pl.emit_grid), dim3(T), (size_t)pl.emit_lds_bytes, st, a);
   if (decode_only) {
     hipLaunchKernelGGL(det_copy_candidates_kernel, dim3(256), dim3(256), 0, st, a);
     RN_LAUNCH_CHECK();
     return RN_OK;
   }
-  return sort_and_suppress(a, L, workspace, st);
+  return sort_and_suppress(a, pl, st);
 }
 }  // namespace
 
@@ -1158,5 +1196,23 @@ extern "C" int rn_nms_classwise(const float* boxes, const float* scores, const i
   hipLaunchKernelGGL(det_zero_seg_kernel, dim3(16), dim3(256), 0, st, a);
   hipLaunchKernelGGL(det_count_arrays_kernel, dim3(256), dim3(256), 0, st, a, count_dev);
   RN_LAUNCH_CHECK();
-  return sort_and_suppress(a, L, workspace, st);
+  rn_det_plan pl;
+  choose_segments(a, L, &pl);
+  return sort_and_suppress(a, pl, st);
+}
+
+extern "C" int rn_detect_plan(const rn_det_level* levels, int nlevels, const rn_det_params* p, rn_det_plan* out) {
+  RN_CHECK_ARG(out, "detect_plan: null plan");
+  DetArgs a = {};
+  WsLayout L;
+  if (nlevels == 0) {   // rn_nms_classwise: the candidates are the caller's arrays
+    RN_CHECK_ARG(p, "detect_plan: null parameters");
+    rn_det_level lv = {nullptr, nullptr, 64};
+    if (int e = plan(&lv, 1, p, &a, &L)) return e;
+    choose_segments(a, L, out);
+    return RN_OK;
+  }
+  if (int e = plan(levels, nlevels, p, &a, &L)) return e;
+  choose(a, L, out);
+  return RN_OK;
 }

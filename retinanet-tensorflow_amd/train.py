@@ -17,6 +17,7 @@ hipGraph -- the launch-bound small kernels of the pyramid's coarse levels then c
 import collections
 import contextlib
 import ctypes
+import gc
 import math
 import os
 import sys
@@ -487,7 +488,7 @@ class GradientAllReduce(object):
             self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM, group=self.group)     # eager first: the communicator connects outside any capture
             torch.cuda.synchronize(device)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            with _no_gc_while_capturing(), torch.cuda.graph(g, capture_error_mode="thread_local"):
                 w = self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM, group=self.group, async_op=True)
                 w.wait()
             want = float(self.world * (self.world + 1) // 2)
@@ -1028,7 +1029,7 @@ class Trainer(object):
         dot = os.environ.get("RN_GRAPH_DOT")       # tuning aid: the captured segment A as a DOT file (nodes = kernels, edges = dependencies)
         ga = torch.cuda.CUDAGraph(keep_graph=True) if dot else torch.cuda.CUDAGraph()
         # thread_local: RCCL's watchdog thread may poll events while the capture is open
-        with torch.cuda.graph(ga, capture_error_mode="thread_local"):
+        with _no_gc_while_capturing(), torch.cuda.graph(ga, capture_error_mode="thread_local"):
             self._graph_out = self.segment_a(self._static)
         if dot:
             hip = ctypes.CDLL("libamdhip64.so")
@@ -1040,7 +1041,7 @@ class Trainer(object):
         gbs, ranges = [], []
         for j in range(self.num_parts()):          # one graph per part of segment B: the collectives go between the replays
             gb = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
+            with _no_gc_while_capturing(), torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
                 ranges.append(self.segment_b(j))   # (deferred weight gradients, if any, are forked AND joined inside the first part)
             gbs.append(gb)
         self._parts = []
@@ -1058,7 +1059,7 @@ class Trainer(object):
         self._warm_up()
         g = torch.cuda.CUDAGraph()
         count, phase = self.opt.step_count, self.opt._phase
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        with _no_gc_while_capturing(), torch.cuda.graph(g, capture_error_mode="thread_local"):
             self._graph_out = self._run_step(self._static)
         self.opt.step_count, self.opt._phase = count, phase      # (recorded, not run: replays count their own steps)
         ranges = [r for r in self.schedule if r[1] <= self.cut_offset]
@@ -1213,6 +1214,23 @@ def _for_each_tensor(tree, fn):
     elif isinstance(tree, (list, tuple)):
         for v in tree:
             _for_each_tensor(v, fn)
+
+
+@contextlib.contextmanager
+def _no_gc_while_capturing():
+    """Around an open stream capture.  torch.cuda.graph no longer collects garbage before it begins a capture, and Python's
+    cyclic collector runs whenever its allocation counters say so: in the middle of a capture it may free an earlier Trainer's
+    graph set (graphs, their memory pool, events) -- device calls a capture does not allow; the process aborts inside the
+    collector.  So: collect before the capture opens, where those calls are harmless and the memory is of use, and keep the
+    collector off until the capture has ended.  (Objects whose last reference goes are freed as ever.)"""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def _clone_tree(tree):
