@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 422
+#define RN_API_VERSION 423
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -404,36 +404,6 @@ int rn_depthwise_bwd(const float* x, const float* dy, const float* wgt, float* d
 int rn_depthwise_wgrad(const float* x, const float* dy, float* dw, int n, int h, int w, int c, int k, int stride,
                        void* workspace, size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer);
 
-/* ------------------------------------------------------------------ fused GroupNorm -> depthwise 3x3 -> GroupNorm
- * The middle of a MobileNetV2 bottleneck, mobilenet_v2.py:56-80 -- Sequential([.., Normalization(), activation, Dropout]),
- * DepthwiseConv2D(3, strides), Normalization(), activation, Dropout --
- *     y = drop2(act(GN2( depthwise3x3_same( drop1(act(GN1(x))) ) )))
- * as ONE kernel forward and ONE backward instead of three each.  A depthwise conv keeps channels apart and both
- * GroupNorms group the same channels, so one block owns a (sample, group) slice end to end, in LDS: exact two-pass
- * statistics, no exchange between blocks, the two intermediate tensors are never written (backward recomputes them
- * from x).  Applies when a slice fits a CU's LDS (rn_dwgn_supported: forward needs h*w*(c/groups)*4 bytes, backward the
- * input and output slices together, <= 156 KB) -- MobileNetV2 at 1/8 resolution and below for a 512^2 image; otherwise
- * the caller runs the three stand-alone kernels.  The dropouts hash (drop_seedK + *drop_seed_dev, element index) exactly
- * like rn_group_norm_fwd, so fused and unfused results agree to rounding.
- */
-typedef struct rn_dwgn_params {
-  int32_t n, h, w, c;      /* input [n,h,w,c]; output [n,ceil(h/stride),ceil(w/stride),c] */
-  int32_t stride;          /* 1 or 2 */
-  int32_t groups, act;     /* of both GroupNorms */
-  float eps, drop_rate;
-  uint64_t drop_seed1, drop_seed2;
-  const uint64_t* drop_seed_dev;
-} rn_dwgn_params;
-int rn_dwgn_supported(const rn_dwgn_params* p, int backward);
-/* stats [4][n][groups]: mean1, rstd1, mean2, rstd2 (kept for the backward pass) */
-int rn_dwgn_fwd(const float* x, const float* gamma1, const float* beta1, const float* wgt, const float* gamma2,
-                const float* beta2, float* y, float* stats, const rn_dwgn_params* p, rn_stream_t stream);
-/* dx [n,h,w,c]; rows: per-sample partial parameter gradients, to be summed over the n rows of each section with
- * rn_reduce_rows: [dgamma1: n x c][dbeta1: n x c][dgamma2: n x c][dbeta2: n x c][dw: n x 9c] */
-int rn_dwgn_bwd(const float* x, const float* dy, const float* gamma1, const float* beta1, const float* wgt,
-                const float* gamma2, const float* beta2, const float* stats, float* dx, float* rows,
-                const rn_dwgn_params* p, rn_stream_t stream);
-
 /* ------------------------------------------------------------------ GroupNorm (+act, +dropout, +residual)
  * Replaces normalization.py:20-35 (reshape + tf.nn.moments + affine), the activation that
  * follows it in every reference Sequential (tf.nn.elu train.py:214 / tf.nn.relu resnet.py:85),
@@ -553,7 +523,7 @@ int rn_upsample_add_bwd_top(const float* dy, float* dtop, int n, int h, int w, i
 /* stand-alone inverted dropout (DenseNet puts tf.layers.Dropout after a conv: densenet.py:44,67,77,143);
  * the same counter-based mask in forward and backward: dx = rn_dropout(dy) with the same seed.
  *
- * THE MASK FUNCTION (every dropout of this library: rn_dropout*, rn_gn_params, rn_dwgn_params, rn_mb_norm).  Element e (flat
+ * THE MASK FUNCTION (every dropout of this library: rn_dropout*, rn_gn_params, rn_mb_norm).  Element e (flat
  * index into the dense NHWC tensor the dropout acts on) with s = seed + (seed_dev ? *seed_dev : 0), all arithmetic mod 2^32:
  *     h  = lo32(e) * 0x9E3779B1 + lo32(s);   h ^= hi32(e) * 0x85EBCA77 + hi32(s);
  *     h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16;
@@ -940,36 +910,6 @@ int rn_mb_depthwise_fwd(const rn_mb_norm* in, const float* w, float* y, int n, i
                         int stat_groups, rn_stream_t stream);
 /* out = dropout(act(GN(in->y))) [+ residual]: writes a normalised tensor out (the end of a chain; tests) */
 int rn_mb_apply(const rn_mb_norm* in, const float* residual, float* out, int n, int hw, rn_stream_t stream);
-
-/* ---- XCD-resident small-map section (csrc/mb_resident.hip): the same forward kernels as PHASES of one launch.
- * For the part of the chain whose per-sample working set fits one XCD's 4 MB L2 (maps of <= 32 x 32 pixels at the BASELINE sizes:
- * bottleneck_4_1's depthwise conv ... bottleneck_7_1 and the output conv of mobilenet_v2.py:120-223, ~33 dependent launches).
- * Grid = 8 x B blocks; the blocks with equal blockIdx.x % 8 sit on one XCD (checked at run time) and work on sample
- * blockIdx.x % 8 (+ 8 ...); between phases they meet at a same-XCD counter barrier (no cache write-back, no cross-XCD fence).
- * A phase = one rn_mb_pointwise_fwd (with `in`; ELU or no activation) or one rn_mb_depthwise_fwd (ELU) call, same meaning of
- * every field.  Statistic rows of resident phases have their OWN layouts (rn_mb_resident_rows): the tiling follows the cluster.
- * Caller's obligations: every buffer written by a phase is written by that phase only and read only by LATER phases of the
- * call; `sync` = rn_mb_resident_sync_bytes() zero-initialised device bytes, private to the stream, written by these launches
- * only.  Word 512 of `sync` is the error word: bit 0 = a barrier wait timed out (a block of the cluster never arrived; the
- * outputs of that call are invalid and the caller must zero `sync` before the next use), bit 1 = a cluster's blocks were seen
- * on two XCDs (placement is not as assumed: results may be stale; stop using the resident path on this device).
- * RN_EUNSUPPORTED: a phase cannot run resident (shape, activation) or the cluster does not fit an XCD -- nothing was launched,
- * use the launch-ordered entry points. */
-enum { RN_MB_PHASE_POINTWISE = 0, RN_MB_PHASE_DEPTHWISE = 1 };
-typedef struct rn_mb_phase {
-  int32_t kind;
-  const rn_mb_norm* in;        /* the GroupNorm block this phase consumes while loading (rows from the previous phase / kernel) */
-  const float* residual;       /* pointwise after a linear block: + residual (or NULL) */
-  float* materialise;          /* pointwise: the formed operand written out once (or NULL) */
-  const float* w; float* y;    /* pointwise: w [cin, cout], y [n, h wd, cout]; depthwise: w [3, 3, c], y [n, oh, ow, c] */
-  int32_t h, wd, cin, cout, stride;   /* the INPUT map; depthwise: cin == cout, stride 1 / 2; pointwise: stride ignored */
-  rn_mb_rows stat_out;         /* y's rows (layout: rn_mb_resident_rows); stat_out.rows == NULL: none */
-  int32_t stat_groups;
-} rn_mb_phase;
-size_t rn_mb_resident_sync_bytes(void);
-/* layout + bytes of the rows a resident phase of this shape emits for a GroupNorm of `groups` groups; 0: cannot run resident */
-size_t rn_mb_resident_rows(int kind, int n, int h, int wd, int cin, int cout, int stride, int groups, rn_mb_rows* layout);
-int rn_mb_resident_fwd(const rn_mb_phase* phases, int nphase, int n, void* sync, rn_stream_t stream);
 
 /* the gradient of a conv output y, as a backward kernel loads it */
 typedef struct rn_mb_dy {

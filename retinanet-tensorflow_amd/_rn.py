@@ -22,7 +22,7 @@ LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
 CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
-API_VERSION = 422        # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 423       # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -140,12 +140,6 @@ class AddSeg(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("count", C.c_int64)]
 
 
-class DwGnParams(C.Structure):
-    _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("stride", C.c_int32),
-                ("groups", C.c_int32), ("act", C.c_int32), ("eps", C.c_float), ("drop_rate", C.c_float),
-                ("drop_seed1", C.c_uint64), ("drop_seed2", C.c_uint64), ("drop_seed_dev", C.c_void_p)]
-
-
 class GnSeg(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("residual", C.c_void_p), ("dy", C.c_void_p),
                 ("dx", C.c_void_p), ("dresidual", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p),
@@ -202,16 +196,6 @@ class MbNorm(C.Structure):
     _fields_ = [("y", C.c_void_p), ("stat", MbRows), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("gamma", C.c_void_p),
                 ("beta", C.c_void_p), ("c", C.c_int32), ("groups", C.c_int32), ("act", C.c_int32), ("eps", C.c_float),
                 ("drop_rate", C.c_float), ("drop_seed", C.c_uint64), ("drop_seed_dev", C.c_void_p)]
-
-
-class MbPhase(C.Structure):
-    """rn_mb_phase: one phase of the XCD-resident section (rn_mb_resident_fwd)"""
-    _fields_ = [("kind", C.c_int32), ("in_", C.POINTER(MbNorm)), ("residual", C.c_void_p), ("materialise", C.c_void_p),
-                ("w", C.c_void_p), ("y", C.c_void_p), ("h", C.c_int32), ("wd", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
-                ("stride", C.c_int32), ("stat_out", MbRows), ("stat_groups", C.c_int32)]
-
-
-MB_PHASE_POINTWISE, MB_PHASE_DEPTHWISE = 0, 1
 
 
 class MbDy(C.Structure):
@@ -293,7 +277,7 @@ SYMBOLS = [
     "rn_winograd_bwd_products_workspace", "rn_winograd_bwd_products", "rn_wino_gn_rows", "rn_conv3x3_winograd_gn", "rn_conv3x3_winograd_gn_bwd", "rn_conv3x3_winograd_gn_bwd_wgrad", "rn_conv3x3_winograd_gn_plan", "rn_reduce_rows", "rn_resize_bilinear_normalize", "rn_resize_pair_u8",
     "rn_resize_pair_u8_augment_workspace", "rn_resize_pair_u8_augment",
     "rn_resize_pair_u8_batch", "rn_resize_pair_u8_augment_batch_workspace", "rn_resize_pair_u8_augment_batch",
-    "rn_dwgn_supported", "rn_dwgn_fwd", "rn_dwgn_bwd", "rn_depthwise_fwd", "rn_depthwise_dgrad", "rn_depthwise_wgrad_workspace", "rn_depthwise_wgrad", "rn_depthwise_bwd",
+    "rn_depthwise_fwd", "rn_depthwise_dgrad", "rn_depthwise_wgrad_workspace", "rn_depthwise_wgrad", "rn_depthwise_bwd",
     "rn_group_norm_sync_bytes", "rn_group_norm_workspace", "rn_group_norm_fwd", "rn_group_norm_bwd", "rn_group_norm_plan",
     "rn_act_fwd", "rn_act_bwd", "rn_upsample_add_fwd", "rn_upsample_add_bwd_top",
     "rn_pack_weights_f16", "rn_pack_weights_f16_bytes", "rn_cast_f32_to_f16", "rn_pad_cast_rgb_f16", "rn_conv2d_fwd_f16", "rn_conv2d_f16_fold_rows", "rn_conv2d_fwd_f16_fold", "rn_group_norm_finalize", "rn_group_norm_apply_f16", "rn_group_norm_apply_res_f16", "rn_maxpool_fwd_f16", "rn_maxpool_gn_fwd_f16", "rn_upsample_add_fwd_f16",
@@ -304,7 +288,7 @@ SYMBOLS = [
     "rn_boxes_decode", "rn_nms_classwise_workspace", "rn_nms_classwise", "rn_detect_plan",
     "rn_optimizer_workspace", "rn_grad_norm_l2reg", "rn_optimizer_update", "rn_counter_add", "rn_add_segs",
     "rn_mb_rows_max", "rn_mb_compact_rows_layout", "rn_mb_compact_rows", "rn_mb_pointwise_rows", "rn_mb_pointwise_fwd", "rn_mb_depthwise_rows", "rn_mb_depthwise_fwd", "rn_mb_apply",
-    "rn_mb_resident_sync_bytes", "rn_mb_resident_rows", "rn_mb_resident_fwd", "rn_set_product_mode", "rn_get_product_mode",
+    "rn_set_product_mode", "rn_get_product_mode",
     "rn_set_x3_bfrag", "rn_get_x3_bfrag", "rn_x3_bfrag_ok", "rn_x3_bfrag_bytes", "rn_x3_pack_bfrag", "rn_gemm_batched_bfrag", "rn_conv3x3_winograd_gn_u_bytes", "rn_conv3x3_winograd_gn_weights",
     "rn_conv2d_f16_stats_tiles", "rn_group_norm_fwd_f16_tiles",
     "rn_mb_pointwise_bwd_rows", "rn_mb_pointwise_bwd_workspace", "rn_mb_pointwise_bwd",
@@ -337,9 +321,6 @@ def lib():
                      "rn_x3_bfrag_bytes", "rn_conv3x3_winograd_gn_u_bytes"):
             getattr(L, name).restype = C.c_size_t
         L.rn_optimizer_workspace.argtypes = [C.c_int64]
-        L.rn_dwgn_supported.argtypes = [C.c_void_p, C.c_int]
-        L.rn_dwgn_fwd.argtypes = [C.c_void_p] * 10
-        L.rn_dwgn_bwd.argtypes = [C.c_void_p] * 12
         L.rn_depthwise_fwd.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]
         L.rn_depthwise_dgrad.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]
         L.rn_depthwise_bwd.argtypes = [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
@@ -492,10 +473,6 @@ def lib():
         for name in ("rn_mb_pointwise_rows", "rn_mb_depthwise_rows", "rn_mb_pointwise_bwd_rows", "rn_mb_pointwise_bwd_workspace",
                      "rn_mb_depthwise_bwd_rows", "rn_mb_depthwise_bwd_workspace"):
             getattr(L, name).restype = C.c_size_t
-        L.rn_mb_resident_sync_bytes.restype = C.c_size_t
-        L.rn_mb_resident_rows.restype = C.c_size_t
-        L.rn_mb_resident_rows.argtypes = [C.c_int] * 8 + [C.c_void_p]
-        L.rn_mb_resident_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.rn_mb_compact_rows_layout.restype = C.c_size_t
         L.rn_mb_compact_rows_layout.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.rn_mb_compact_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -590,7 +567,7 @@ def sync_counters(device):
     capturing = torch.cuda.is_current_stream_capturing() if device.type == 'cuda' else False
     key = (device.type, device.index, h if h in SIDE_STREAMS else 0)
     if key[2] == 0:
-        _hand_over(('gn',) + key, h, device)
+        _hand_over(key, h, device)
     t = _sync_words.get(key)
     if t is None:
         if capturing:
@@ -600,8 +577,7 @@ def sync_counters(device):
     return t
 
 
-_resident_words = {}
-_region_owner = {}      # region key -> raw handle of the stream that used the shared "main stream" region last
+_region_owner = {}     # region key -> raw handle of the stream that used the shared "main stream" region last
 
 
 def _hand_over(key, h, device):
@@ -625,51 +601,15 @@ def _hand_over(key, h, device):
         _region_owner[key] = h
 
 
-def resident_sync(device):
-    """The zeroed region (rn_mb_resident_sync_bytes()) per (device, main / side stream) for rn_mb_resident_fwd: the clusters'
-    barrier counters; word 512 is the error word (bit 0: a wait timed out, bit 1: a cluster was not on one XCD).  Same keying
-    as sync_counters: every stream that is not a registered side stream is 'the main stream'."""
-    h = stream().value or 0
-    key = (device.type, device.index, h if h in SIDE_STREAMS else 0)
-    if key[2] == 0:
-        _hand_over(('mb',) + key, h, device)
-    t = _resident_words.get(key)
-    if t is None:
-        if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
-            raise RnError("the resident section's counters must exist before graph capture (run the step once eagerly)")
-        t = torch.zeros(lib().rn_mb_resident_sync_bytes() // 4, dtype=torch.int32, device=device)
-        _resident_words[key] = t
-    return t
-
-
-def resident_errors():
-    """OR of the resident sections' error words over all regions (0: fine; synchronises)."""
-    e = 0
-    for t in _resident_words.values():
-        e |= int(t[512].item())
-    return e
-
-
-def barrier_timeout_sources():
-    """(GroupNorm exchange regions with their error word set, MobileNetV2 resident-section counter sets with theirs set)."""
-    return (sum(int(t[2].item()) for t in {id(t): t for t in _sync_words.values()}.values()),
-            sum(1 for t in _resident_words.values() if int(t[512].item()) != 0))
-
-
 def barrier_timeouts():
-    """Number of (device, stream) counter sets whose error word is set (should always be 0): the grid-resident GroupNorm's
-    exchange regions and the MobileNetV2 resident section's clusters."""
-    return (sum(int(t[2].item()) for t in {id(t): t for t in _sync_words.values()}.values()) +
-            sum(1 for t in _resident_words.values() if int(t[512].item()) != 0))
+    """Number of (device, stream) exchange regions of the grid-resident GroupNorm whose error word is set (should always be 0)."""
+    return sum(int(t[2].item()) for t in {id(t): t for t in _sync_words.values()}.values())
 
 
 def reset_barrier_timeouts():
-    """Clear the error words (after the caller has dealt with a reported timeout, e.g. by switching the path off); the
-    resident section's counters are zeroed entirely (a timed-out launch leaves them dirty)."""
+    """Clear the error words (after the caller has dealt with a reported timeout, e.g. by switching the path off)."""
     for t in {id(t): t for t in _sync_words.values()}.values():
         t[2] = 0
-    for t in _resident_words.values():
-        t.zero_()
 
 
 def side_stream(device, index=0):

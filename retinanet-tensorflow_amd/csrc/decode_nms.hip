@@ -240,7 +240,7 @@ __device__ __forceinline__ void scan_wave_lds(const DetArgs& a, const DetLevel& 
     for (int j = 0; j < 8; ++j) {
       const int g = g0 + j * 64 + lane;
       if (g < total) {
-        const int r = (int)(((float)g + 0.5f) * inv_cv), ch = g - r * CV;     // exact for these sizes (see dw_gn.hip fast_div)
+        const int r = (int)(((float)g + 0.5f) * inv_cv), ch = g - r * CV;     // exact for these sizes: (g + 0.5) / CV is off by < 1e-6 g / CV, inside the 0.5 / CV margin
         *reinterpret_cast<uint4*>(lds + r * RS + ch * 16) = t[j];
       }
     }

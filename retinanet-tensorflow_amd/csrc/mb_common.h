@@ -1,5 +1,5 @@
-// Shared device / host helpers of the MobileNetV2 bottleneck-chain kernels (mbconv.hip: the launch-ordered kernels;
-// mb_resident.hip: the XCD-resident small-map section): statistic rows, per-channel tables, the counter-based dropout mask,
+// Device / host helpers of the MobileNetV2 bottleneck-chain kernels (mbconv.hip): statistic rows, per-channel tables, the
+// counter-based dropout mask,
 // argument structs of the forward kernels, tile / slab planning.  Not part of the public ABI.  Everything lives in an
 // anonymous namespace: each translation unit gets its own copy, the kernels inline what they use.
 #pragma once

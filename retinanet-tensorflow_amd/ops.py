@@ -212,9 +212,6 @@ def end_deferred_reductions():
         cur = torch.cuda.current_stream()
         try:
             _rn.check(L.rn_flush_reductions(C.byref(_defer_lists[cur.cuda_stream]), _rn.stream()), "rn_flush_reductions")
-            for st in _midway_streams:             # the flushes started midway (their inputs stay alive in _deferred_keep until here)
-                cur.wait_stream(st)
-            del _midway_streams[:]
             for st in _deferred_streams:
                 # fork again from the current stream first: after autograd's end-of-backward join a side stream is no
                 # longer part of an ongoing hipGraph capture, and its flush would run eagerly instead of being captured
@@ -225,29 +222,6 @@ def end_deferred_reductions():
         finally:
             del _deferred_keep[:]
             del _deferred_streams[:]
-
-
-FLUSH_MIDWAY = os.environ.get("RN_FLUSH_MIDWAY", "0") == "1"     # measured: 446 vs 450 images/s -- off (a fork / join edge costs more than the tail it shortens)
-
-
-def flush_deferred_midway(device):
-    """Run the row reductions recorded so far on the current stream NOW, on a side stream (index 4), and go on recording: a
-    long backward node (the MobileNetV2 chain: ~50 reductions, most of them recorded while the small maps are processed) then
-    leaves only its last few for the flush that sits on the critical path after the last backward kernel.  The side stream is
-    joined by end_deferred_reductions (and by _rn.join_side_streams)."""
-    if not (_deferring and FLUSH_MIDWAY):
-        return
-    cur = torch.cuda.current_stream()
-    lst = _defer_lists.get(cur.cuda_stream)
-    if lst is None or lst.count == 0:
-        return
-    side = _rn.side_stream(device, 4)
-    side.wait_stream(cur)
-    _rn.check(_rn.lib().rn_flush_reductions(C.byref(lst), C.c_void_p(side.cuda_stream)), "rn_flush_reductions")
-    _midway_streams.append(side)
-
-
-_midway_streams = []
 
 
 def _grad_workspace(need, device):
@@ -800,78 +774,6 @@ def depthwise_conv2d(x, w, stride=1, gn=None):
             return y
         return outs
     return _Depthwise.apply(x, w, stride)
-
-
-# GroupNorm -> depthwise 3x3 -> GroupNorm of a MobileNetV2 bottleneck as one kernel per direction (rn_dwgn_fwd / rn_dwgn_bwd).
-# Correct (tests/test_gpu_ops.py::test_fused_groupnorm_depthwise_groupnorm) but OFF by default: measured on the headline step it
-# is slower than the three kernels it replaces (347 vs 360 images/s; forward 19-40 us vs ~27, backward 58 vs ~41 per
-# bottleneck): one block per (sample, group) is 64 blocks on 256 CUs, and with one channel lane per thread the stencil's index
-# arithmetic (~100 VALU instructions per output) makes those 64 CUs ALU-bound.  See DESIGN.md section 9.
-DW_GN_FUSED = os.environ.get("RN_DW_GN_FUSED", "0") == "1"
-
-
-def _dwgn_params(x, stride, groups, eps, act, rate, seed1, seed2, seed_dev):
-    n, h, w, c = x if isinstance(x, tuple) else x.shape
-    return _rn.DwGnParams(n, h, w, c, stride, groups, _rn.ACT[act], eps, rate, seed1, seed2,
-                          seed_dev.data_ptr() if seed_dev is not None else None)
-
-
-def dw_gn_ok(shape, w, stride, groups, act, need_backward):
-    """Can drop(act(GN(dw3x3(drop(act(GN(x))))))) run as the fused kernels for an fp32 device tensor x of `shape` [n,h,w,c]?"""
-    if not (DW_GN_FUSED and w.is_cuda and len(shape) == 4 and w.shape[0] == 3 and w.shape[1] == 3 and w.shape[2] == shape[3]
-            and stride in (1, 2) and act in (None, "none", "relu", "elu", "relu6")):
-        return False
-    p = _dwgn_params(tuple(int(v) for v in shape), stride, groups, 1e-5, act, 0.0, 0, 0, None)
-    return bool(_rn.lib().rn_dwgn_supported(C.byref(p), 1 if need_backward else 0))
-
-
-class _DwGnFused(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, cfg, x, g1, b1, w, g2, b2):
-        stride, groups, eps, act, rate, seed1, seed2, seed_dev = cfg
-        x = x.contiguous()
-        n, h, wd, c = x.shape
-        oh, _ = _rn.same_pad(h, 3, stride)
-        ow, _ = _rn.same_pad(wd, 3, stride)
-        y = torch.empty((n, oh, ow, c), dtype=torch.float32, device=x.device)
-        stats = torch.empty((4, n, groups), dtype=torch.float32, device=x.device)
-        p = _dwgn_params(x, stride, groups, eps, act, rate, seed1, seed2, seed_dev)
-        _rn.check(_rn.lib().rn_dwgn_fwd(_rn.f32(x), _rn.f32(g1), _rn.f32(b1), _rn.f32(w), _rn.f32(g2), _rn.f32(b2), _rn.f32(y),
-                                        _rn.f32(stats), C.byref(p), _rn.stream()), "rn_dwgn_fwd")
-        ctx.cfg = cfg
-        ctx.save_for_backward(x, g1, b1, w, g2, b2, stats)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        stride, groups, eps, act, rate, seed1, seed2, seed_dev = ctx.cfg
-        x, g1, b1, w, g2, b2, stats = ctx.saved_tensors
-        n, h, wd, c = x.shape
-        L = _rn.lib()
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        rows = torch.empty((13 * n * c,), dtype=torch.float32, device=x.device)
-        if _deferring:
-            _deferred_keep.append(rows)
-        p = _dwgn_params(x, stride, groups, eps, act, rate, seed1, seed2, seed_dev)
-        _rn.check(L.rn_dwgn_bwd(_rn.f32(x), _rn.f32(dy), _rn.f32(g1), _rn.f32(b1), _rn.f32(w), _rn.f32(g2), _rn.f32(b2),
-                                _rn.f32(stats), _rn.f32(dx), _rn.f32(rows), C.byref(p), _rn.stream()), "rn_dwgn_bwd")
-        grads = []
-        nc = n * c
-        for i, prm in enumerate((g1, b1, g2, b2, w)):
-            buf, ret = _grad_slot(prm)
-            count = 9 * c if i == 4 else c
-            sec = rows[i * nc:i * nc + n * count]
-            _rn.check(L.rn_reduce_rows(_rn.f32(sec), _rn.f32(buf), count, n, 0, _rn.stream(), _defer_arg()), "rn_reduce_rows")
-            grads.append(ret)
-        dg1, db1, dg2, db2, dw = grads                    # rows order; the inputs are (x, g1, b1, w, g2, b2)
-        return None, dx, dg1, db1, dw, dg2, db2
-
-
-def dw_gn_fused(x, gamma1, beta1, w, gamma2, beta2, stride, groups, eps, act, rate=0.0, seed1=0, seed2=0, seed_dev=None):
-    """drop2(act(GN2(depthwise3x3(drop1(act(GN1(x))))))): see rn_dwgn_fwd."""
-    cfg = (int(stride), int(groups), float(eps), act, float(rate), int(seed1), int(seed2), seed_dev)
-    return _DwGnFused.apply(cfg, x, gamma1, beta1, w, gamma2, beta2)
 
 
 def gn_groups(c, groups=32):

@@ -879,19 +879,6 @@ class Trainer(object):
         if not self._parts:
             return None
         rng = None
-        probe = int(os.environ.get("RN_PROBE_SIDE_PRODUCTS", "0"))   # tuning aid: N head-tower-sized batched products on a side
-        side = None                                                   # stream beside the backbone's backward pass
-        if probe and self.device.type == 'cuda':
-            pm = int(os.environ.get("RN_PROBE_M", "682"))
-            if not hasattr(self, "_probe_buf"):
-                self._probe_buf = (torch.randn(36, pm, 256, device=self.device), torch.randn(36, 256, 256, device=self.device) * 0.01,
-                                   torch.empty(36, pm, 256, device=self.device))
-            A_, B_, C_ = self._probe_buf
-            main, side = torch.cuda.current_stream(), _rn.side_stream(self.device, 6)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                for _ in range(probe):
-                    _rn.check(_rn.lib().rn_gemm_batched(_rn.f32(A_), _rn.f32(B_), _rn.f32(C_), A_.shape[1], 256, 256, 36, 0, _rn.stream()), "rn_gemm_batched")
         if self._deferred_wgrads:             # the towers' weight-gradient halves: forked off here
             self._fork_wgrads(after_wgrads)
         skip = () if join_wgrads else (self.WGRAD_STREAM,)
@@ -899,8 +886,6 @@ class Trainer(object):
             roots, seeds, rng = self._parts[j]
             with self._scoped():
                 self._backward(roots, [l.grad for l in seeds], skip_join=skip)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
         if part is None:
             self._parts = []
             return (0, self.cut_offset)
@@ -1126,11 +1111,10 @@ class Trainer(object):
         if feed is not None:
             feed.consumed()
         self.steps_done += 1
-        # (only the opt-in waiting kernels -- the grid-resident GroupNorm, the XCD-resident MobileNetV2 section -- can flag
-        # anything; checked after the first steps too, not only every check_interval: a poisoned update must not be trained on
-        # for long.  The same check on every path, the one-graph step included.)
-        import ops_mb
-        if (self.check_interval and (ops.GN_GRID_RESIDENT or ops_mb.RESIDENT)
+        # (only the opt-in waiting kernels -- the grid-resident GroupNorm -- can flag anything; checked after the first steps
+        # too, not only every check_interval: a poisoned update must not be trained on for long.  The same check on every
+        # path, the one-graph step included.)
+        if (self.check_interval and ops.GN_GRID_RESIDENT
                 and (self.steps_done in (1, 2, 4, 8) or self.steps_done % self.check_interval == 0)):
             self.check_device_errors()
         self.last = {'class_loss': class_loss, 'regr_loss': regr_loss,
@@ -1181,28 +1165,21 @@ class Trainer(object):
         return float(sum(a.elapsed_time(b) for a, b in ev) / len(ev))
 
     def check_device_errors(self):
-        """Raise if any kernel of this process has flagged an error on the device (synchronises).  Two opt-in kernel families
-        wait for co-resident blocks and can time out: the grid-resident GroupNorm (ops.GN_GRID_RESIDENT) and the XCD-resident
-        MobileNetV2 section (ops_mb.RESIDENT); the one that flagged is the one switched off."""
-        import ops_mb
-        n_gn, n_mb = _rn.barrier_timeout_sources()
+        """Raise if any kernel of this process has flagged an error on the device (synchronises).  One opt-in kernel family
+        waits for co-resident blocks and can time out: the grid-resident GroupNorm (ops.GN_GRID_RESIDENT); it is switched off
+        when it has flagged."""
+        n_gn = _rn.barrier_timeouts()
         if self.allreduce.active:       # every rank must take the same decision, or the others hang in the next all-reduce
-            t = torch.tensor([float(n_gn), float(n_mb)], device=self.device)
+            t = torch.tensor([float(n_gn)], device=self.device)
             self.allreduce.dist.all_reduce(t, op=self.allreduce.dist.ReduceOp.MAX, group=self.allreduce.group)
-            n_gn, n_mb = int(t[0].item()), int(t[1].item())
-        if n_gn or n_mb:
-            what = []
-            if n_gn:
-                ops.GN_GRID_RESIDENT = False        # the launch-ordered kernels from here on (on every rank: the counts are maxima over ranks)
-                what.append("%d GroupNorm exchange wait(s) (ops.GN_GRID_RESIDENT is now False)" % n_gn)
-            if n_mb:
-                ops_mb.RESIDENT = False
-                what.append("%d MobileNetV2 resident-section barrier(s) (ops_mb.RESIDENT is now False)" % n_mb)
+            n_gn = int(t[0].item())
+        if n_gn:
+            ops.GN_GRID_RESIDENT = False        # the launch-ordered kernels from here on (on every rank: the count is a maximum over ranks)
             _rn.reset_barrier_timeouts()
             self._graphs = None                 # the captured graphs contain the waiting kernels: capture again ...
             self._graph_cache.clear()           # ... for every input shape
-            raise _rn.RnError("timed out on some rank: %s: the updates since the last check are invalid -- reload the last "
-                              "checkpoint and continue" % "; ".join(what))
+            raise _rn.RnError("timed out on some rank: %d GroupNorm exchange wait(s) (ops.GN_GRID_RESIDENT is now False): the updates "
+                              "since the last check are invalid -- reload the last checkpoint and continue" % n_gn)
 
 
 def _for_each_tensor(tree, fn):

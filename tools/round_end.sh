@@ -34,9 +34,6 @@ rm -rf $OUT/${R}_nms_prof
 timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/${R}_nms_prof -o nms -- python tools/nms_prof.py stress > $OUT/${R}_nms_stress.log 2>&1
 python tools/by_grid.py $(find $OUT/${R}_nms_prof -name "nms_kernel_trace.csv" | head -1) > $OUT/${R}_nms_stress_kernels_by_grid.txt
 rm -rf $OUT/${R}_nms_prof $OUT/${R}_prof $OUT/${R}_pmc_fetch $OUT/${R}_pmc_write
-[ -z "$QUICK" ] && (hipcc --offload-arch=gfx950 -O3 tools/micro/boundary.hip -o /tmp/boundary && /tmp/boundary > $OUT/${R}_micro_boundary.txt 2>&1)
-[ -z "$QUICK" ] && (hipcc --offload-arch=gfx950 -O3 tools/micro/xcd_cluster.hip -o /tmp/xcd_cluster && timeout 300 /tmp/xcd_cluster > $OUT/${R}_micro_xcd_cluster.txt 2>&1)
-[ -z "$QUICK" ] && (RN_MB_RESIDENT=1 timeout 300 python tools/mb_resident_phases.py 512 2 > $OUT/${R}_mb_resident_phases.txt 2>&1)
 [ -z "$QUICK" ] && (timeout 300 python tools/x3_bench.py > $OUT/${R}_x3_products.txt 2>&1; for v in 0 1 2 4 8 15; do echo "RN_X3_DBG=$v $(env RN_X3_DBG=$v timeout 300 python tools/x3_bench.py 2>&1 | grep 'mode 1' | tail -1)"; done > $OUT/${R}_x3_leave_one_out.txt 2>&1)
 [ -z "$QUICK" ] && (timeout 600 python tools/f16_trained_probe.py 2500 1e-2 2>&1 | tail -8 > $OUT/${R}_f16_trained_probe.txt)
 [ -z "$QUICK" ] && (timeout 400 python tools/f16_layer_probe.py > $OUT/${R}_f16_layers.txt 2>&1; timeout 300 python tools/bench_inference.py > $OUT/${R}_inference_lines.txt 2>&1)
