@@ -363,9 +363,46 @@ typedef struct rn_f16_fold {
   int32_t total_chunks;
 } rn_f16_fold;
 int rn_conv2d_f16_fold_rows(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g);
-/* m-tiles per sample each segment of such a launch would write statistics rows for (0: none) */
+/* m-tiles per sample each segment of such a launch would write statistics rows for (0: none); RN_EUNSUPPORTED where the several-segment
+ * layout is not possible: fp32 output, cout/groups % 8 != 0, groups, and a shape the super-group kernel takes */
 int rn_conv2d_f16_stats_tiles(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int32_t* tiles_per_sample);
 int rn_conv2d_fwd_f16_fold(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, const rn_f16_fold* fold, rn_stream_t stream);
+/* What one rn_conv2d_fwd_f16 (fold == NULL) / rn_conv2d_fwd_f16_fold call with the same arguments launches (host only).  It is the
+ * decision the launch is made from: conv_f16_impl (csrc/conv_f16.hip) fills an rn_f16_plan and launches from it; the query is the
+ * same function stopped before the first launch and before the pipelined kernels' dynamic-LDS attribute is requested.  It touches
+ * no device and follows no data pointer: segs[].x / wgt / y / bias and the fold's in_* / partial are only compared with NULL where
+ * the entry point does that (fold->seg_chunk_start is a host array and is read as the entry point reads it).  Returns what the
+ * launch would return for the same arguments (RN_EINVAL / RN_EUNSUPPORTED; RN_EINVAL for a NULL plan or an empty fold); the plan
+ * of a refused call is not meaningful.  rn_conv2d_f16_fold_rows and rn_conv2d_f16_stats_tiles read rows_per_sample /
+ * tiles_per_sample of the plan of the plain fp16-output call.
+ * Environment switches, as the entry points read them.  At every call: RN_CONV_CFG.  Once per process (first use): RN_F16_SG,
+ * RN_F16_PIPE, RN_F16_NT, RN_F16_PIPE_MIN_K.
+ * `pipe` is the K loop the host asks for; the pipelined kernels need 147 KB of dynamic LDS, an attribute only a device can grant:
+ * rn_conv2d_f16_pipe_available (device side: the same one-time request the first pipelined launch makes) returns 1 when it was
+ * granted, 0 when every launch with pipe != 0 silently runs the plain loop (the same template F, PIPE = 0) instead. */
+enum rn_f16_kernel { RN_F16_KERNEL_IGEMM = 1 /* conv_f16_kernel */, RN_F16_KERNEL_SG = 2 /* conv3x3_sg32_f16_kernel */ };
+enum rn_f16_epilogue { RN_F16_EPI_STAGED = 0 /* fp16 through LDS, 16-byte stores */, RN_F16_EPI_SCALAR_F16 = 1, RN_F16_EPI_SCALAR_F32 = 2 };
+typedef struct rn_f16_plan {
+  int32_t kernel;          /* enum rn_f16_kernel */
+  int32_t cfg;             /* implicit GEMM: tile 0 128x128, 1 128x64, 2 64x64, 3 128x32, 4 256x128, 5 256x256; super-group: the stride 1 / 2 */
+  int32_t vec;             /* halfs per operand gather: 4 or 8 */
+  int32_t tap_uniform;     /* every K tile lies inside one filter tap (cin/G % 64 == 0) */
+  int32_t fold;            /* implicit GEMM: the template's F (0, 2 statistics, 3 input fold + statistics, 7 the same with ReLU);
+                              super-group: FIN (0 none, 1 any activation, 2 ReLU) */
+  int32_t stats;           /* the epilogue writes statistic rows (implicit GEMM: F & 2) */
+  int32_t pipe;            /* 0 the plain loop, 1 pipelined with both operands through LDS, 2 weight fragments from the packed copy */
+  int32_t epilogue;        /* enum rn_f16_epilogue */
+  int32_t a_nt;            /* non-temporal loads of the activation operand */
+  int32_t frag_copy;       /* every segment's wgt_bytes proves the fragment-ordered copy */
+  int32_t blocks;          /* grid size */
+  int32_t k_tiles;         /* K tiles of 64 halfs (super-group: 18 matrix-core steps, reported as 0) */
+  int32_t rows_per_sample; /* statistic rows per sample of a one-segment fold (rn_conv2d_f16_fold_rows; 0: the shape cannot fold) */
+  int32_t multi_stats;     /* the several-segment statistics layout is possible (fp16 output, cout % 8 == 0, no groups) */
+  int32_t tiles_per_sample[RN_MAX_SEG]; /* ... and the rows per sample each segment writes there (rn_conv2d_f16_stats_tiles) */
+} rn_f16_plan;
+int rn_conv2d_f16_plan(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int out_f32, const rn_f16_fold* fold /* NULL: rn_conv2d_fwd_f16 */,
+                       rn_f16_plan* plan);
+int rn_conv2d_f16_pipe_available(void);
 /* mean / rstd [n][groups] from the partial sums above (fp64, fixed order); hw = oh * ow */
 int rn_group_norm_finalize(const float* partial, int n, int rows_per_sample, int hw, int c, int groups, float eps, float* mean,
                            float* rstd, rn_stream_t stream);

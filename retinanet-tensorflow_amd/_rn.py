@@ -186,6 +186,19 @@ class F16Fold(C.Structure):
                 ("seg_chunk_start", C.c_void_p), ("total_chunks", C.c_int32)]
 
 
+class F16Plan(C.Structure):
+    """rn_f16_plan: the kernel one rn_conv2d_fwd_f16 / rn_conv2d_fwd_f16_fold call launches (rn_conv2d_f16_plan, host only)"""
+    _fields_ = [("kernel", C.c_int32), ("cfg", C.c_int32), ("vec", C.c_int32), ("tap_uniform", C.c_int32), ("fold", C.c_int32),
+                ("stats", C.c_int32), ("pipe", C.c_int32), ("epilogue", C.c_int32), ("a_nt", C.c_int32), ("frag_copy", C.c_int32),
+                ("blocks", C.c_int32), ("k_tiles", C.c_int32), ("rows_per_sample", C.c_int32), ("multi_stats", C.c_int32),
+                ("tiles_per_sample", C.c_int32 * MAX_SEG)]
+
+
+# enum rn_f16_kernel / rn_f16_epilogue
+F16_KERNELS = {0: None, 1: "igemm", 2: "sg"}
+F16_EPILOGUES = {0: "staged", 1: "scalar_f16", 2: "scalar_f32"}
+
+
 class MbRows(C.Structure):
     """rn_mb_rows"""
     _fields_ = [("rows", C.c_void_p), ("rows_per_sample", C.c_int32), ("width", C.c_int32), ("bn", C.c_int32)]
@@ -290,7 +303,7 @@ SYMBOLS = [
     "rn_mb_rows_max", "rn_mb_compact_rows_layout", "rn_mb_compact_rows", "rn_mb_pointwise_rows", "rn_mb_pointwise_fwd", "rn_mb_depthwise_rows", "rn_mb_depthwise_fwd", "rn_mb_apply",
     "rn_set_product_mode", "rn_get_product_mode",
     "rn_set_x3_bfrag", "rn_get_x3_bfrag", "rn_x3_bfrag_ok", "rn_x3_bfrag_bytes", "rn_x3_pack_bfrag", "rn_gemm_batched_bfrag", "rn_conv3x3_winograd_gn_u_bytes", "rn_conv3x3_winograd_gn_weights",
-    "rn_conv2d_f16_stats_tiles", "rn_group_norm_fwd_f16_tiles",
+    "rn_conv2d_f16_stats_tiles", "rn_group_norm_fwd_f16_tiles", "rn_conv2d_f16_plan", "rn_conv2d_f16_pipe_available",
     "rn_mb_pointwise_bwd_rows", "rn_mb_pointwise_bwd_workspace", "rn_mb_pointwise_bwd",
     "rn_mb_depthwise_bwd_rows", "rn_mb_depthwise_bwd_workspace", "rn_mb_depthwise_bwd", "rn_set_mb_dw_taps", "rn_get_mb_dw_taps",
     "rn_debug_collective_standin", "rn_optimizer_norm_pairs", "rn_norm_reg_finalize",
@@ -385,6 +398,9 @@ def lib():
                                               [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.rn_x3_bfrag_ok.argtypes = [C.c_int] * 3
         L.rn_conv2d_f16_stats_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rn_conv2d_f16_plan"):    # (added without an ABI bump, like the entries below: a library from before it still loads)
+            L.rn_conv2d_f16_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(F16Plan)]
+            L.rn_conv2d_f16_pipe_available.argtypes = []
         L.rn_group_norm_fwd_f16_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_conv3x3_winograd_gn_u_bytes.argtypes = [C.c_int] * 3
         L.rn_conv3x3_winograd_gn_weights.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

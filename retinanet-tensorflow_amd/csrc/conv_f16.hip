@@ -923,10 +923,22 @@ extern "C" int rn_pad_cast_rgb_f16(const float* x, void* y, int64_t pixels, rn_s
 }
 
 namespace {
-// fold == nullptr: the plain convolution.  rows_out != nullptr: dry run -- *rows_out = m-tile rows per sample the statistics
-// would take (0: this shape cannot fold), nothing is launched.
-int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int out_f32, const rn_f16_fold* fold, int* rows_out,
-                  rn_stream_t stream, int* tiles_out = nullptr) {
+// The dynamic-LDS attribute of the pipelined kernels, requested once per process (only a device can grant it).
+bool pipe_attr_ok() {
+  constexpr size_t lds = 2 * (256 + 256) * LDH * sizeof(_Float16);
+  static const bool attr_ = (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
+                            (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
+                            (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
+                            (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
+                            (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 7, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
+  return attr_;
+}
+
+// fold == nullptr: the plain convolution.  *p is filled and the launch is made from it; plan_only: the query (rn_conv2d_f16_plan,
+// _fold_rows, _stats_tiles) -- nothing is launched and no device is touched.
+int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int out_f32, const rn_f16_fold* fold, rn_f16_plan* p,
+                  bool plan_only, rn_stream_t stream) {
+  *p = rn_f16_plan{};
   RN_CHECK_ARG(segs && g && nseg >= 1 && nseg <= RN_MAX_SEG, "conv f16: bad segments");
   RN_CHECK_ARG(g->kh >= 1 && g->kw >= 1 && g->stride >= 1 && g->cin >= 1, "conv f16: bad geometry");
   const int G = g->groups > 1 ? g->groups : 1;
@@ -935,6 +947,7 @@ int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int 
   a.nseg = nseg; a.kh = g->kh; a.kw = g->kw; a.stride = g->stride; a.cin = g->cin;
   a.groups = G; a.cin_g = g->cin / G; a.out_f32 = out_f32 ? 1 : 0;
   RN_UNSUPPORTED(a.cin_g % 4 != 0, "conv f16: input channels per group (%d) must be a multiple of 4", a.cin_g);
+  p->frag_copy = 1;
   for (int s = 0; s < nseg; ++s) {
     RN_CHECK_ARG(segs[s].x && segs[s].wgt && segs[s].y && segs[s].n >= 1 && segs[s].h >= 1 && segs[s].w >= 1 &&
                  segs[s].cout >= 1 && segs[s].cout % G == 0, "conv f16: bad segment %d", s);
@@ -947,6 +960,7 @@ int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int 
       const int64_t kk = (int64_t)g->kh * g->kw * (g->cin / G), off = frag_offset_halfs(kk, segs[s].cout);
       const bool there = off && segs[s].wgt_bytes >= (int64_t)rn_pack_weights_f16_bytes(g->kh, g->kw, g->cin / G, segs[s].cout);
       d.wf = there ? d.wt + off : nullptr;
+      if (!there) p->frag_copy = 0;
     }
     d.n = segs[s].n; d.h = segs[s].h; d.w = segs[s].w; d.cout = segs[s].cout;
     rn::same_pad(d.h, g->kh, g->stride, &d.oh, &d.pad_t);
@@ -959,6 +973,7 @@ int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int 
                    "conv f16: a tensor of segment %d is >= 2 GiB", s);
   }
   const int cout_g = a.seg[0].cout / G;
+  p->epilogue = out_f32 ? RN_F16_EPI_SCALAR_F32 : ((cout_g & 7) == 0 ? RN_F16_EPI_STAGED : RN_F16_EPI_SCALAR_F16);
   {
     // ResNeXt's conv 2 on 16 x 16 pixel tiles of 32-channel super-groups (conv3x3_sg32_f16_kernel); RN_F16_SG=0: the implicit GEMM
     static const bool sg_on = !(getenv("RN_F16_SG") && atoi(getenv("RN_F16_SG")) == 0);
@@ -971,7 +986,6 @@ int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int 
     if (shape_ok) {
       const int th = S_ == 1 ? 16 : 8;
       const int rows = (d.h / S_ / th) * (d.w / S_ / 16);
-      if (rows_out) { *rows_out = rows; return RN_OK; }
       G3Args ga = {};
       ga.x = d.x; ga.ws = d.wt + so; ga.y = (_Float16*)d.y; ga.partial = fold ? fold->partial : nullptr;
       ga.n = d.n; ga.h = d.h; ga.w = d.w; ga.c = d.cout; ga.tiles_w = d.w / S_ / 16; ga.tiles_per_sample = rows; ga.nsg = d.cout / 32;
@@ -984,16 +998,19 @@ int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int 
         ga.in_groups = fold->in_groups; ga.in_cpg = g->cin / fold->in_groups; ga.in_act = fold->in_act;
         fin = fold->in_act == RN_ACT_RELU ? 2 : 1;
       }
-      const unsigned blocks = (unsigned)((long)d.n * rows * ga.nsg);
+      p->kernel = RN_F16_KERNEL_SG; p->cfg = S_; p->vec = 8; p->tap_uniform = 1; p->fold = fin; p->stats = ga.partial != nullptr;
+      p->blocks = (int32_t)((long)d.n * rows * ga.nsg); p->rows_per_sample = rows;
+      if (plan_only) return RN_OK;
+      const unsigned blocks = (unsigned)p->blocks;
       hipStream_t st_ = (hipStream_t)stream;
 #define RN_G3(S__)                                                                                                          \
       do {                                                                                                                      \
-        if (fin == 2) hipLaunchKernelGGL((conv3x3_sg32_f16_kernel<true, 2, S__>), dim3(blocks), dim3(256), 0, st_, ga);           \
-        else if (fin == 1) hipLaunchKernelGGL((conv3x3_sg32_f16_kernel<true, 1, S__>), dim3(blocks), dim3(256), 0, st_, ga);      \
-        else if (ga.partial) hipLaunchKernelGGL((conv3x3_sg32_f16_kernel<true, 0, S__>), dim3(blocks), dim3(256), 0, st_, ga);    \
+        if (p->fold == 2) hipLaunchKernelGGL((conv3x3_sg32_f16_kernel<true, 2, S__>), dim3(blocks), dim3(256), 0, st_, ga);       \
+        else if (p->fold == 1) hipLaunchKernelGGL((conv3x3_sg32_f16_kernel<true, 1, S__>), dim3(blocks), dim3(256), 0, st_, ga);  \
+        else if (p->stats) hipLaunchKernelGGL((conv3x3_sg32_f16_kernel<true, 0, S__>), dim3(blocks), dim3(256), 0, st_, ga);      \
         else hipLaunchKernelGGL((conv3x3_sg32_f16_kernel<false, 0, S__>), dim3(blocks), dim3(256), 0, st_, ga);                   \
       } while (0)
-      if (S_ == 1) RN_G3(1); else RN_G3(2);
+      if (p->cfg == 1) RN_G3(1); else RN_G3(2);
 #undef RN_G3
       RN_LAUNCH_CHECK();
       return RN_OK;
@@ -1043,32 +1060,39 @@ int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int 
     const double bytes = (double)d0.n * d0.h * d0.w * d0.x_ld * 2.0;
     a.a_nt = once && (nt_mode >= 0 ? nt_mode != 0 : bytes >= 33554432.0);
   }
+  p->kernel = RN_F16_KERNEL_IGEMM; p->cfg = c; p->vec = vec8 ? 8 : 4; p->tap_uniform = tapu; p->a_nt = a.a_nt; p->blocks = tiles;
+  p->k_tiles = rn::ceil_div(g->kh * g->kw * a.cin_g, BK);
+  {
+    // what a fold of this call could write: one segment -- a tile's rows must lie inside one sample, the fp16 staged epilogue must
+    // be the one that runs (rn_conv2d_f16_fold_rows); several segments, output statistics only -- every segment whose m-tiles lie
+    // inside one sample (rn_conv2d_f16_stats_tiles; a segment whose tiles straddle samples, P7: 64 pixels per sample, gets 0)
+    const int ohw0 = a.seg[0].oh * a.seg[0].ow;
+    p->rows_per_sample = (nseg == 1 && !out_f32 && (cout_g & 7) == 0 && ohw0 % kCfgs[c].bm == 0) ? ohw0 / kCfgs[c].bm : 0;
+    p->multi_stats = !(out_f32 || (cout_g & 7) != 0 || G != 1);
+    for (int s = 0; s < nseg; ++s) {
+      const int ohw = a.seg[s].oh * a.seg[s].ow;
+      p->tiles_per_sample[s] = (p->multi_stats && ohw % kCfgs[c].bm == 0) ? ohw / kCfgs[c].bm : 0;
+    }
+  }
   int fbits = 0;
-  if (tiles_out || (fold && fold->seg_chunk_start)) {
+  if (fold && fold->seg_chunk_start) {
     // Several segments (the head towers' pyramid levels in one launch), output statistics only: every segment whose m-tiles lie
     // inside one sample writes its rows into ONE array [2][total_chunks][cout] at its own first row (seg_chunk_start[s]; its
-    // rows: sample-major, tiles_out[s] per sample); a segment whose tiles straddle samples (P7: 64 pixels per sample) gets 0.
-    RN_UNSUPPORTED(out_f32 || (cout_g & 7) != 0 || G != 1, "conv f16 stats: fp16 output, cout %% 8 == 0, no groups");
-    RN_UNSUPPORTED(fold && fold->in_mean, "conv f16 stats: several segments fold the output side only");
+    // rows: sample-major, tiles_per_sample[s] per sample).
+    RN_UNSUPPORTED(!p->multi_stats, "conv f16 stats: fp16 output, cout %% 8 == 0, no groups");
+    RN_UNSUPPORTED(fold->in_mean, "conv f16 stats: several segments fold the output side only");
     for (int s = 0; s < nseg; ++s) {
       SegH& d = a.seg[s];
-      const int ohw = d.oh * d.ow, t = ohw % kCfgs[c].bm == 0 ? ohw / kCfgs[c].bm : 0;
-      if (tiles_out) { tiles_out[s] = t; continue; }
       RN_CHECK_ARG(d.bias == nullptr && fold->partial && fold->total_chunks >= 1, "conv f16 stats: bias-free conv, a partial array");
-      d.partial = t ? fold->partial + (size_t)fold->seg_chunk_start[s] * d.cout : nullptr;
+      d.partial = p->tiles_per_sample[s] ? fold->partial + (size_t)fold->seg_chunk_start[s] * d.cout : nullptr;
       d.prows = fold->total_chunks;
     }
-    if (tiles_out) return RN_OK;
     fbits = 2;
-  } else if (fold || rows_out) {
-    // a tile's rows must lie inside one sample, the fp16 staged epilogue must be the one that runs, one segment
+  } else if (fold) {
     const SegH& d = a.seg[0];
-    const int ohw = d.oh * d.ow;
     // (the output statistics do not care how the operands are gathered: the RGB stem's 4-channel vectors qualify; the input-side
     // fold transforms whole 8-channel vectors)
-    const bool ok = nseg == 1 && !out_f32 && (cout_g & 7) == 0 && ohw % kCfgs[c].bm == 0;
-    if (rows_out) { *rows_out = ok ? ohw / kCfgs[c].bm : 0; return RN_OK; }
-    RN_UNSUPPORTED(!ok, "conv f16 fold: this shape cannot fold its GroupNorms (see rn_conv2d_f16_fold_rows)");
+    RN_UNSUPPORTED(!p->rows_per_sample, "conv f16 fold: this shape cannot fold its GroupNorms (see rn_conv2d_f16_fold_rows)");
     RN_UNSUPPORTED(fold->in_mean && !vec8, "conv f16 fold: a GroupNorm on the operand load needs input channels in multiples of 8");
     if (fold->in_mean) {
       RN_CHECK_ARG(fold->in_rstd && fold->in_gamma && fold->in_beta && fold->in_groups >= 1 && g->cin % fold->in_groups == 0,
@@ -1081,56 +1105,53 @@ int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int 
     RN_UNSUPPORTED(!fold->partial, "conv f16 fold: the input-side fold is built together with the output statistics only (pass `partial`)");
     if (fold->partial) {
       RN_CHECK_ARG(d.bias == nullptr, "conv f16 fold: the statistics are those of a bias-free conv (the GroupNorm behind it absorbs a bias)");
-      a.fold.partial = fold->partial; a.fold.prows = d.n * (ohw / kCfgs[c].bm);
+      a.fold.partial = fold->partial; a.fold.prows = d.n * p->rows_per_sample;
       a.seg[0].partial = fold->partial; a.seg[0].prows = a.fold.prows;
       fbits |= 2;
     }
   }
-  hipStream_t st = (hipStream_t)stream;
-#define RN_F16K(BM_, BN_, WM_, WN_, F_)                                                                             \
-  do {                                                                                                              \
-    if (tapu) hipLaunchKernelGGL((conv_f16_kernel<BM_, BN_, WM_, WN_, 8, true, F_>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
-    else hipLaunchKernelGGL((conv_f16_kernel<BM_, BN_, WM_, WN_, 8, false, F_>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
-  } while (0)
-#define RN_F16(BM_, BN_, WM_, WN_)                                                                                  \
-  do {                                                                                                              \
-    if (fbits == 2 && vec8) RN_F16K(BM_, BN_, WM_, WN_, 2);                                                    \
-    else if (fbits == 3 && a.fold.in_act == RN_ACT_RELU) RN_F16K(BM_, BN_, WM_, WN_, 7);                            \
-    else if (fbits == 3) RN_F16K(BM_, BN_, WM_, WN_, 3);                                                            \
-    else if (vec8) RN_F16K(BM_, BN_, WM_, WN_, 0);                                                                  \
-    else if (fbits == 2) hipLaunchKernelGGL((conv_f16_kernel<BM_, BN_, WM_, WN_, 4, false, 2>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
-    else hipLaunchKernelGGL((conv_f16_kernel<BM_, BN_, WM_, WN_, 4, false, 0>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
-  } while (0)
+  p->fold = fbits == 3 ? (a.fold.in_act == RN_ACT_RELU ? 7 : 3) : fbits;
+  p->stats = (fbits & 2) != 0;
   // the 256 x 256 tile, dense taps, no input-side fold: the software-pipelined variants (147 KB of dynamic LDS); RN_F16_PIPE: 0 the
   // plain loop, 1 both operands through LDS, 2 (default) the weight fragments straight from the fragment-ordered copy
   static const int pipe_mode = getenv("RN_F16_PIPE") ? atoi(getenv("RN_F16_PIPE")) : 2;
   // (an input-side fold rides along where it is a ReLU GroupNorm in front of a 1 x 1 conv: ResNeXt's conv 3)
   const bool fin_pipe = fbits == 3 && pipe_mode == 2 && g->kh == 1 && g->kw == 1 && g->stride == 1 && a.fold.in_act == RN_ACT_RELU &&
                         nseg == 1 && a.seg[0].wf != nullptr;
-  if (c == 5 && tapu && pipe_mode && G == 1 && (fbits == 0 || fbits == 2 || fin_pipe)) {
+  if (c == 5 && tapu && pipe_mode && G == 1 && (fbits == 0 || fbits == 2 || fin_pipe))
+    p->pipe = (fin_pipe || (pipe_mode == 2 && p->frag_copy)) ? 2 : 1;
+  if (plan_only) return RN_OK;
+
+  hipStream_t st = (hipStream_t)stream;
+  // (the attribute refused: the plain loop below computes the same bits from 36 KB of static LDS)
+  if (p->pipe && pipe_attr_ok()) {
     constexpr size_t lds = 2 * (256 + 256) * LDH * sizeof(_Float16);
-    static const bool attr_ = (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
-                              (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
-                              (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
-                              (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
-                              (hipFuncSetAttribute((const void*)conv_f16_kernel<256, 256, 2, 4, 8, true, 7, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
-    if (attr_) {           // (refused: the plain loop below computes the same bits from 36 KB of static LDS)
-      bool frag = pipe_mode == 2;
-      for (int s = 0; s < nseg; ++s) frag = frag && a.seg[s].wf != nullptr;
-      if (fin_pipe) {
-        hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 7, 2>), dim3(tiles), dim3(512), lds, st, a);
-      } else if (frag) {
-        if (fbits == 2) hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 2, 2>), dim3(tiles), dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 0, 2>), dim3(tiles), dim3(512), lds, st, a);
-      } else {
-        if (fbits == 2) hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 2, 1>), dim3(tiles), dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 0, 1>), dim3(tiles), dim3(512), lds, st, a);
-      }
-      RN_LAUNCH_CHECK();
-      return RN_OK;
+    if (p->pipe == 2) {
+      if (p->fold == 7) hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 7, 2>), dim3(tiles), dim3(512), lds, st, a);
+      else if (p->fold == 2) hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 2, 2>), dim3(tiles), dim3(512), lds, st, a);
+      else hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 0, 2>), dim3(tiles), dim3(512), lds, st, a);
+    } else {
+      if (p->fold == 2) hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 2, 1>), dim3(tiles), dim3(512), lds, st, a);
+      else hipLaunchKernelGGL((conv_f16_kernel<256, 256, 2, 4, 8, true, 0, 1>), dim3(tiles), dim3(512), lds, st, a);
     }
+    RN_LAUNCH_CHECK();
+    return RN_OK;
   }
-  switch (c) {
+#define RN_F16K(BM_, BN_, WM_, WN_, F_)                                                                             \
+  do {                                                                                                              \
+    if (p->tap_uniform) hipLaunchKernelGGL((conv_f16_kernel<BM_, BN_, WM_, WN_, 8, true, F_>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
+    else hipLaunchKernelGGL((conv_f16_kernel<BM_, BN_, WM_, WN_, 8, false, F_>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
+  } while (0)
+#define RN_F16(BM_, BN_, WM_, WN_)                                                                                  \
+  do {                                                                                                              \
+    if (p->vec == 8 && p->fold == 2) RN_F16K(BM_, BN_, WM_, WN_, 2);                                                \
+    else if (p->fold == 7) RN_F16K(BM_, BN_, WM_, WN_, 7);                                                          \
+    else if (p->fold == 3) RN_F16K(BM_, BN_, WM_, WN_, 3);                                                          \
+    else if (p->vec == 8) RN_F16K(BM_, BN_, WM_, WN_, 0);                                                           \
+    else if (p->fold == 2) hipLaunchKernelGGL((conv_f16_kernel<BM_, BN_, WM_, WN_, 4, false, 2>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
+    else hipLaunchKernelGGL((conv_f16_kernel<BM_, BN_, WM_, WN_, 4, false, 0>), dim3(tiles), dim3(WM_* WN_ * 64), 0, st, a); \
+  } while (0)
+  switch (p->cfg) {
     case 0: RN_F16(128, 128, 2, 2); break;
     case 1: RN_F16(128, 64, 2, 2); break;
     case 2: RN_F16(64, 64, 2, 2); break;
@@ -1146,21 +1167,37 @@ int conv_f16_impl(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int 
 }  // namespace
 
 extern "C" int rn_conv2d_fwd_f16(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int out_f32, rn_stream_t stream) {
-  return conv_f16_impl(segs, nseg, g, out_f32, nullptr, nullptr, stream);
+  rn_f16_plan plan;
+  return conv_f16_impl(segs, nseg, g, out_f32, nullptr, &plan, false, stream);
 }
 
+extern "C" int rn_conv2d_f16_plan(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int out_f32, const rn_f16_fold* fold,
+                                  rn_f16_plan* plan) {
+  RN_CHECK_ARG(plan, "conv f16 plan: null plan");
+  RN_CHECK_ARG(!fold || fold->in_mean || fold->partial, "conv f16 fold: nothing to fold");
+  return conv_f16_impl(segs, nseg, g, out_f32, fold, plan, true, nullptr);
+}
+
+extern "C" int rn_conv2d_f16_pipe_available(void) { return pipe_attr_ok() ? 1 : 0; }
+
 extern "C" int rn_conv2d_f16_fold_rows(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g) {
-  int rows = 0;
-  if (conv_f16_impl(segs, nseg, g, 0, nullptr, &rows, nullptr) != RN_OK) return 0;
-  return rows;
+  rn_f16_plan plan;
+  if (conv_f16_impl(segs, nseg, g, 0, nullptr, &plan, true, nullptr) != RN_OK) return 0;
+  return plan.rows_per_sample;
 }
 
 extern "C" int rn_conv2d_f16_stats_tiles(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, int32_t* tiles_per_sample) {
   RN_CHECK_ARG(tiles_per_sample, "conv f16 stats tiles: null argument");
-  return conv_f16_impl(segs, nseg, g, 0, nullptr, nullptr, nullptr, tiles_per_sample);
+  rn_f16_plan plan;
+  const int e = conv_f16_impl(segs, nseg, g, 0, nullptr, &plan, true, nullptr);
+  if (e != RN_OK) return e;
+  RN_UNSUPPORTED(plan.kernel != RN_F16_KERNEL_IGEMM || !plan.multi_stats, "conv f16 stats: fp16 output, cout %% 8 == 0, no groups");
+  for (int s = 0; s < nseg; ++s) tiles_per_sample[s] = plan.tiles_per_sample[s];
+  return RN_OK;
 }
 
 extern "C" int rn_conv2d_fwd_f16_fold(const rn_conv_seg* segs, int nseg, const rn_conv_geom* g, const rn_f16_fold* fold, rn_stream_t stream) {
   RN_CHECK_ARG(fold && (fold->in_mean || fold->partial), "conv f16 fold: nothing to fold");
-  return conv_f16_impl(segs, nseg, g, 0, fold, nullptr, stream);
+  rn_f16_plan plan;
+  return conv_f16_impl(segs, nseg, g, 0, fold, &plan, false, stream);
 }
