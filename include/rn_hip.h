@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 423
+#define RN_API_VERSION 424
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -743,6 +743,45 @@ int rn_loss_terms_fwd(const rn_loss_seg* segs, int nseg, int num_classes, const 
                       float* class_loss_out, float* regr_loss_out, void* workspace, size_t workspace_bytes, rn_stream_t stream);
 int rn_loss_terms_bwd(const rn_loss_seg* segs, int nseg, int num_classes, const rn_loss_terms* t, const float* stats,
                       const float* g_cls, const float* g_reg, rn_stream_t stream);
+
+/* ------------------------------------------------------------------ box regression loss as a weighted sum of terms
+ * Replaces regression_loss (losses.py:144-152) by a sum over the set terms of weight * term, over the foreground rows (fg:
+ * trainable and max_c cls_label[row, c] > 0.5, the rule of rn_loss_fwd).  Prediction p and label l of a row are the anchor-relative
+ * (ty, tx, th, tw) of dataset.py:102-112 / utils.py:100-117; in anchor units box(t) = (ty - e^th/2, tx - e^tw/2, ty + e^th/2,
+ * tx + e^tw/2), I = the area of the intersection, U = area(p) + area(l) - I, E = the area of the smallest enclosing box:
+ *   RN_RT_HUBER  sum_fg huber_delta(l - p) / (4 #fg)      (regression_loss, losses.py:144-152; delta: tf.losses.huber_loss's)
+ *   RN_RT_IOU    sum_fg (1 - I/U) / #fg
+ *   RN_RT_GIOU   sum_fg (1 - (I/U - (E - U)/E)) / #fg
+ * Both boxes of a row share the anchor, so regression_postprocess (utils.py:108-117) maps them to the image by one translation and
+ * one positive per-axis scaling, under which ratios of areas (utils.iou, utils.py:62-97) do not change: no anchor table is read.
+ * DIoU / CIoU (centre distance over diagonal) are not invariant under an anisotropic scaling, would need per-row anchor aspect
+ * ratios, and are not covered.  The loss is 0 with #fg = 0.  th / tw are not clamped (regression_postprocess does not clamp).
+ * Subgradients: max(P, L) follows P where P >= L, min(P, L) where P <= L, max(0, d) passes where d > 0.
+ * Masking: HUBER is the fg weight times the term on every trainable row (a NaN on a trainable row reaches the loss, as in
+ * rn_loss_fwd); IOU and GIOU select: a row that is not fg adds exactly 0 and gets gradient exactly 0 whatever it holds.  Rows
+ * outside the trainable mask are never read into a sum.  Sums: per-block partials, fixed-order fp64 finalize, no atomics.
+ *
+ * rn_regr_terms_fwd reads cls_label (for the fg rule only), reg_pred, reg_label and trainable of each segment (cls_logit and the
+ * d_* fields may be null) and writes stats, regr_loss_out (optional) and fg_rows (caller-owned, sum of rows bytes, segment order:
+ * 1 for a fg row, else 0).  rn_regr_terms_bwd reads reg_pred, reg_label, fg_rows, stats and the device scalar g_reg and writes
+ * every element of d_reg_pred = d(g_reg * regr_loss)/d(reg_pred), zeros on rows that are not fg; it touches no class tensor.
+ * Zero-row segments are allowed, as in rn_loss_fwd.  No allocation, no synchronisation, no host read: both record into a graph.
+ * The descriptor is read before the call returns.  RN_EINVAL (rn_last_error names the field): null descriptor; no term or an
+ * unknown bit set; w_* / delta_huber of a set term not finite or <= 0; w_* / delta_huber of a clear term not 0; nseg outside
+ * 1..RN_MAX_SEG. */
+enum rn_regr_term { RN_RT_HUBER = 1, RN_RT_IOU = 2, RN_RT_GIOU = 4 };
+typedef struct rn_regr_terms {
+  uint32_t terms;                    /* OR of rn_regr_term */
+  float w_huber, w_iou, w_giou;      /* > 0 for a set term, 0 for a clear one */
+  float delta_huber;                 /* > 0 with RN_RT_HUBER, else 0 */
+} rn_regr_terms;
+#define RN_REGR_STATS_FLOATS 8   /* [0] regr_loss [1] #fg [2] sum huber [3] sum (1-IoU) [4] sum (1-GIoU) [5] sum IoU [6,7] reserved */
+/* 0 (and rn_last_error) for a descriptor rn_regr_terms_fwd would refuse */
+size_t rn_regr_terms_workspace(const rn_loss_seg* segs, int nseg, int num_classes, const rn_regr_terms* t);
+int rn_regr_terms_fwd(const rn_loss_seg* segs, int nseg, int num_classes, const rn_regr_terms* t, float* stats,
+                      float* regr_loss_out, uint8_t* fg_rows, void* workspace, size_t workspace_bytes, rn_stream_t stream);
+int rn_regr_terms_bwd(const rn_loss_seg* segs, int nseg, const rn_regr_terms* t, const float* stats, const uint8_t* fg_rows,
+                      const float* g_reg, rn_stream_t stream);
 
 /* ------------------------------------------------------------------ running training metrics
  * Replaces build_metrics (train.py:137-161): the streaming tf.metrics of a training run -- the means of the total, class,

@@ -22,7 +22,7 @@ LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
 CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
-API_VERSION = 423       # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 424       # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -239,6 +239,17 @@ class LossTerms(C.Structure):
                 ("s_dice", C.c_float), ("s_jaccard", C.c_float), ("s_fixed_iou", C.c_float)]
 
 
+# enum rn_regr_term; the names are those of losses.parse_regr_loss and of the w_ fields below
+REGR_TERM = {"huber": 1, "iou": 2, "giou": 4}
+REGR_STATS_FLOATS = 8    # RN_REGR_STATS_FLOATS
+
+
+class RegrTerms(C.Structure):
+    """rn_regr_terms (passed by pointer, read before the call returns): weight and delta of a clear term stay 0."""
+    _fields_ = [("terms", C.c_uint32), ("w_huber", C.c_float), ("w_iou", C.c_float), ("w_giou", C.c_float),
+                ("delta_huber", C.c_float)]
+
+
 class MetricsSeg(C.Structure):
     """rn_metrics_seg: one pyramid level of rn_train_metrics_pass"""
     _fields_ = [("cls_logit", C.c_void_p), ("cls_label", C.c_void_p), ("reg_pred", C.c_void_p), ("reg_label", C.c_void_p),
@@ -297,6 +308,7 @@ SYMBOLS = [
     "rn_act_fwd_f16", "rn_flip_width", "rn_dropout", "rn_dropout_strided", "rn_maxpool_fwd", "rn_maxpool_bwd", "rn_maxpool_bwd_arg", "rn_avgpool_fwd", "rn_avgpool_bwd",
     "rn_loss_workspace", "rn_loss_fwd", "rn_loss_bwd",
     "rn_loss_terms_stats_floats", "rn_loss_terms_workspace", "rn_loss_terms_fwd", "rn_loss_terms_bwd",
+    "rn_regr_terms_workspace", "rn_regr_terms_fwd", "rn_regr_terms_bwd",
     "rn_iou", "rn_anchor_assign", "rn_anchor_assign_levels", "rn_anchor_assign_levels_pair", "rn_decode_boxes", "rn_detect_workspace", "rn_detect",
     "rn_boxes_decode", "rn_nms_classwise_workspace", "rn_nms_classwise", "rn_detect_plan",
     "rn_optimizer_workspace", "rn_grad_norm_l2reg", "rn_optimizer_update", "rn_counter_add", "rn_add_segs",
@@ -467,6 +479,11 @@ def lib():
                                         C.c_void_p, C.c_size_t, C.c_void_p]
         L.rn_loss_terms_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LossTerms), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]
+        L.rn_regr_terms_workspace.restype = C.c_size_t
+        L.rn_regr_terms_workspace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RegrTerms)]
+        L.rn_regr_terms_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RegrTerms), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rn_regr_terms_bwd.argtypes = [C.c_void_p, C.c_int, C.POINTER(RegrTerms), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_iou.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_anchor_assign.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + \
                                       [C.c_void_p] * 4 + [C.c_void_p]

@@ -1051,6 +1051,69 @@ def detection_loss(cls_logits, reg_preds, cls_labels, reg_labels, trainable_mask
                                 *trainable_masks)
 
 
+class _RegressionTerms(torch.autograd.Function):
+    """(regr_loss, stats) of a losses.RegrLoss over all levels (csrc/regr_terms.hip); only reg_preds carry a gradient."""
+
+    @staticmethod
+    def forward(ctx, spec, num_classes, n, *tensors):
+        reg_preds = [t.contiguous() for t in tensors[:n]]
+        reg_labels = [t.contiguous() for t in tensors[n:2 * n]]
+        cls_labels = [t.contiguous() for t in tensors[2 * n:3 * n]]
+        masks = [t.contiguous() for t in tensors[3 * n:4 * n]]
+        for p, l, c, m in zip(reg_preds, reg_labels, cls_labels, masks):
+            assert m.dtype in (torch.uint8, torch.bool)
+            assert p.dtype == l.dtype == c.dtype == torch.float32
+            assert p.shape == l.shape and p.numel() == 4 * m.numel() and c.numel() == num_classes * m.numel()
+        L = _rn.lib()
+        dev = reg_preds[0].device
+        desc = spec.struct()
+        segs = (_rn.LossSeg * n)()
+        for i in range(n):
+            segs[i].cls_label, segs[i].reg_pred, segs[i].reg_label = _rn.f32(cls_labels[i]), _rn.f32(reg_preds[i]), _rn.f32(reg_labels[i])
+            segs[i].trainable = _rn.ptr(masks[i])
+            segs[i].rows = masks[i].numel()
+        stats = torch.empty((_rn.REGR_STATS_FLOATS,), dtype=torch.float32, device=dev)
+        regr_loss = torch.empty((), dtype=torch.float32, device=dev)
+        fg_rows = torch.empty((sum(m.numel() for m in masks),), dtype=torch.uint8, device=dev)
+        ws = _rn.workspace(L.rn_regr_terms_workspace(segs, n, num_classes, C.byref(desc)), dev)
+        _rn.check(L.rn_regr_terms_fwd(segs, n, num_classes, C.byref(desc), _rn.f32(stats), _rn.f32(regr_loss), _rn.ptr(fg_rows),
+                                      ws.data_ptr(), ws.numel(), _rn.stream()), "rn_regr_terms_fwd")
+        ctx.spec, ctx.n = spec, n
+        ctx.save_for_backward(stats, fg_rows, *reg_preds, *reg_labels)
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+        return regr_loss, stats
+
+    @staticmethod
+    def backward(ctx, g_reg, _g_stats):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        stats, fg_rows = saved[0], saved[1]
+        reg_preds, reg_labels = list(saved[2:2 + n]), list(saved[2 + n:2 + 2 * n])
+        if g_reg is None:
+            g_reg = torch.zeros((1,), dtype=torch.float32, device=stats.device)
+        g_reg = g_reg.reshape(1).contiguous().float()
+        dreg = [torch.empty_like(r) for r in reg_preds]
+        segs = (_rn.LossSeg * n)()
+        for i in range(n):
+            segs[i].reg_pred, segs[i].reg_label = _rn.f32(reg_preds[i]), _rn.f32(reg_labels[i])
+            segs[i].d_reg_pred = _rn.f32(dreg[i])
+            segs[i].rows = reg_preds[i].numel() // 4
+        _rn.check(_rn.lib().rn_regr_terms_bwd(segs, n, C.byref(ctx.spec.struct()), _rn.f32(stats), _rn.ptr(fg_rows), _rn.f32(g_reg),
+                                              _rn.stream()), "rn_regr_terms_bwd")
+        return (None, None, None) + tuple(dreg) + (None,) * (3 * n)
+
+
+def regression_terms(reg_preds, reg_labels, cls_labels, trainable_masks, num_classes, spec):
+    """The box regression loss as a weighted sum of Huber / IoU / GIoU terms over the foreground rows (rn_regr_terms_fwd /
+    rn_regr_terms_bwd).  Lists over pyramid levels; spec: a regression-loss spec / losses.RegrLoss.  Returns (regr_loss, stats);
+    stats (RN_REGR_STATS_FLOATS floats: loss, #fg, sum huber, sum (1 - IoU), sum (1 - GIoU), sum IoU) carries no gradient."""
+    import losses
+    spec = losses.parse_regr_loss(spec)
+    n = len(reg_preds)
+    return _RegressionTerms.apply(spec, num_classes, n, *reg_preds, *reg_labels, *cls_labels, *trainable_masks)
+
+
 class _Dropout(torch.autograd.Function):
     """tf.layers.Dropout on its own (DenseNet: after a conv).  Same counter-based mask both ways."""
 

@@ -566,7 +566,7 @@ class Trainer(object):
                  loss_mode='bce_dice', device='cuda', use_graph=False, process_group=None,
                  direct_param_grads=True, wgrad_side_stream=False, defer_reductions=True, overlap=True,
                  force_collective=False, input_fn=None, check_interval=50, capture_collectives=None, lr_schedule=None,
-                 ema_decay=None, ema_warmup=True, accumulate_steps=1, skip_nonfinite=False, train_metrics=False):
+                 ema_decay=None, ema_warmup=True, accumulate_steps=1, skip_nonfinite=False, train_metrics=False, regr_loss=None):
         self.net, self.levels = net, levels or build_levels()
         self.device = torch.device(device)
         if self.device.type == 'cuda':
@@ -580,6 +580,9 @@ class Trainer(object):
         # loss_mode: 'bce_dice' / 'focal' (None: losses.LOSS_MODE), or a class-loss spec (losses.parse_class_loss: a weighted sum of the reference's terms),
         # parsed here so that a bad one fails before anything is built; the loss stays two nodes of the step's graph either way
         self.loss_mode = loss_mode if (loss_mode is None or loss_mode in _rn.LOSS_MODE) else losses.parse_class_loss(loss_mode)
+        # regr_loss: None (the Huber loss of the class-loss kernels), or a regression-loss spec (losses.parse_regr_loss: a weighted sum
+        # of Huber, IoU and GIoU terms), parsed here as well; a spec other than 'huber:1:1' adds three nodes to the step's graph
+        self.regr_loss = None if regr_loss is None else losses.parse_regr_loss(regr_loss)
         self.arena = ParamArena(net, self.device)
         # lr_schedule (LRSchedule): the rate lives on the device and advances inside the step (Optimizer docstring); None: the
         # constant `learning_rate`, a launch argument
@@ -818,7 +821,7 @@ class Trainer(object):
                 torch.cuda.current_stream().wait_stream(label_stream)
             inp, logits = utils.process_labels_and_logits(labels=features, logits=logits, levels=self.levels)
             class_loss, regr_loss = losses.loss(labels=inp['detection_trainable'], logits=logits['detection_trainable'],
-                                                mode=self.loss_mode)
+                                                mode=self.loss_mode, regr_mode=self.regr_loss)
             if self.metrics is not None:       # on this stream, before the backward pass: every tensor it reads is alive and ordered
                 self.metrics.update(inp['detection_trainable'], logits['detection_trainable'], self.levels,
                                     tuple(features['image'].shape[1:3]))
@@ -1294,6 +1297,11 @@ def build_parser():
                              'NAME[:WEIGHT[:SMOOTH]] joined by +, NAME one of %s, SMOOTH for dice / jaccard / fixed_iou only '
                              '(defaults 0 / 1 / 1e-7), e.g. bce+jaccard or balanced_bce+dice:0.5; not with --loss focal'
                              % ', '.join(losses.TERM_NAMES))
+    parser.add_argument('--regr-loss', type=str, default=None, metavar='SPEC',
+                        help='the box regression loss as a weighted sum of terms over the foreground anchors: huber[:WEIGHT[:DELTA]] '
+                             '(the reference\'s regression_loss; DELTA defaults to 1), iou[:WEIGHT] and giou[:WEIGHT] (1 - IoU and '
+                             '1 - GIoU of the predicted and the label box), joined by +, e.g. giou:2 or huber:0.5+giou:2; '
+                             'left out: huber alone, as before')
     parser.add_argument('--steps-per-epoch', type=int, default=None,
                         help='default: 100 for shapes, NUM for shapes PATH NUM SIZE, one pass of the shard for a file dataset')
     parser.add_argument('--shape-runs', type=int, default=None,
@@ -1362,6 +1370,17 @@ def train_metrics_suffix(res):
     return (' | mean total %.4f class %.4f regr %.4f reg %.4f class_iou %.4f regr_iou %.4f over %d steps' % (
         res['total_loss'], res['class_loss'], res['regr_loss'], res['regularization_loss'], res['class_iou'], res['regr_iou'],
         res['steps']) + (' (%d non-finite left out)' % res['nonfinite_steps'] if res['nonfinite_steps'] > 0 else ''))
+
+
+def regr_loss_flag_error(args):
+    """What is wrong with --regr-loss as given (checked before any dataset or device is touched), or None."""
+    if getattr(args, 'regr_loss', None) is None:
+        return None
+    try:
+        losses.parse_regr_loss(args.regr_loss)
+    except ValueError as e:
+        return '--regr-loss: %s' % e
+    return None
 
 
 def class_loss_flag_error(args):
@@ -1531,6 +1550,8 @@ def main(argv=None):
         parser.error(guard_flag_error(args))
     if class_loss_flag_error(args):
         parser.error(class_loss_flag_error(args))
+    if regr_loss_flag_error(args):
+        parser.error(regr_loss_flag_error(args))
     K = args.samples_per_step
     if K != 1 and not files:
         parser.error('--samples-per-step groups raw uint8 image files: it needs --dataset pascal ... or coco ...')
@@ -1608,9 +1629,12 @@ def main(argv=None):
                       input_fn=feed, **({'lr_schedule': lr_schedule} if lr_schedule is not None else {}),
                       **({'ema_decay': args.ema_decay, 'ema_warmup': not args.ema_no_warmup} if args.ema_decay is not None else {}),
                       **({'accumulate_steps': A} if A > 1 else {}), **({'skip_nonfinite': True} if args.skip_nonfinite else {}),
-                      **({'train_metrics': True} if args.train_metrics else {}))
+                      **({'train_metrics': True} if args.train_metrics else {}),
+                      **({'regr_loss': args.regr_loss} if args.regr_loss is not None else {}))
     if args.class_loss is not None and rank == 0:
         print('class loss: %s' % trainer.loss_mode.describe(), flush=True)
+    if args.regr_loss is not None and rank == 0:
+        print('regr loss: %s' % trainer.regr_loss.describe(), flush=True)
 
     def skipped():
         return check_nonfinite_limit(trainer, args.nonfinite_limit)
