@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 424
+#define RN_API_VERSION 425
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -440,6 +440,35 @@ int rn_depthwise_bwd(const float* x, const float* dy, const float* wgt, float* d
                      int stride, void* workspace, size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer);
 int rn_depthwise_wgrad(const float* x, const float* dy, float* dw, int n, int h, int w, int c, int k, int stride,
                        void* workspace, size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer);
+
+/* Which kernels the rn_depthwise_* calls of this shape launch, and with which grids -- for tests that must know which
+ * implementation a shape takes.  It is the decision the entry points themselves run before they launch (one function).  Host
+ * only: touches no device, launches nothing.  groups: of the GroupNorm behind rn_depthwise_fwd_stats (< 1: the stats_* fields
+ * stay 0).  Returns what rn_depthwise_fwd / _dgrad would return for the same shape (RN_EINVAL / RN_EUNSUPPORTED: the plan is
+ * zeroed), RN_EINVAL for a NULL plan. */
+enum rn_dw_fwd {
+  RN_DW_FWD_K3 = 1,      /* dw_fwd_kernel<true>: unrolled, branch-free 3x3 */
+  RN_DW_FWD_GENERIC = 2  /* dw_fwd_kernel<false>: any k                    */
+};
+enum rn_dw_dgrad {
+  RN_DW_DGRAD_K3_PARITY = 1, /* dw_dgrad_kernel<true> at stride 2: the 2 x 2 taps whose parity matches the pixel's */
+  RN_DW_DGRAD_K3 = 2,        /* dw_dgrad_kernel<true> at any other stride: nine taps under divisibility masks       */
+  RN_DW_DGRAD_GENERIC = 3    /* dw_dgrad_kernel<false>: any k                                                       */
+};
+typedef struct rn_dw_plan {
+  int32_t oh, ow, pad_t, pad_l;         /* SAME geometry: output size, padding before                                       */
+  int32_t fwd_kernel, fwd_blocks;       /* rn_dw_fwd; blocks of 256 threads (at most 8192: grid-stride)                     */
+  int32_t dgrad_kernel, dgrad_blocks;   /* rn_dw_dgrad; likewise                                                            */
+  int32_t wgrad_ok;                     /* 0: rn_depthwise_wgrad and rn_depthwise_bwd return RN_EUNSUPPORTED (k != 3)       */
+  int32_t wgrad_chunks, wgrad_ppc;      /* blocks of dw_wgrad_partial_kernel (at most 4096) and output pixels of each       */
+  int32_t bwd_blocks;                   /* dw_bwd_kernel: dgrad_blocks + wgrad_chunks (0 where wgrad_ok is 0)               */
+  int32_t stats_r;                      /* dw_fwd_stats_kernel<R>: 4, 8, 16; 0: rn_depthwise_stats_rows returns 0           */
+  int32_t stats_ppc;                    /* output pixels per block                                                          */
+  int32_t stats_rows_per_sample;        /* = rn_gn_rows.rows_per_sample                                                     */
+  int32_t stats_blocks;                 /* n * stats_rows_per_sample                                                        */
+  uint64_t wgrad_workspace_bytes;       /* = rn_depthwise_wgrad_workspace                                                   */
+} rn_dw_plan;
+int rn_depthwise_plan(int n, int h, int w, int c, int k, int stride, int groups, rn_dw_plan* plan);
 
 /* ------------------------------------------------------------------ GroupNorm (+act, +dropout, +residual)
  * Replaces normalization.py:20-35 (reshape + tf.nn.moments + affine), the activation that

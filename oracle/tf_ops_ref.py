@@ -116,7 +116,11 @@ def activation(x, kind):
     if kind == "relu":
         return F.relu(x)
     if kind == "relu6":
-        return torch.clamp(x, 0.0, 6.0)
+        # [TF-sem] Relu6Grad passes the gradient where 0 < x < 6, both ends excluded: hardtanh's backward does the same
+        # (clamp's passes it AT 0 and 6); the forward values are those of clamp
+        return F.hardtanh(x, 0.0, 6.0)
+    if kind == "sigmoid":
+        return torch.sigmoid(x)
     raise ValueError(kind)
 
 

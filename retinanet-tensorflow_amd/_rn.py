@@ -22,7 +22,7 @@ LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
 CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
-API_VERSION = 424       # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 425       # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -287,6 +287,20 @@ DET_EMITS = {0: None, 1: "HIST", 2: "STRIDED"}
 DET_SEGMENTS = {1: "LDS_SCATTER", 2: "GLOBAL_SCATTER"}
 
 
+class DwPlan(C.Structure):
+    """rn_dw_plan: the kernels the rn_depthwise_* calls of one shape launch (rn_depthwise_plan, host only)"""
+    _fields_ = [("oh", C.c_int32), ("ow", C.c_int32), ("pad_t", C.c_int32), ("pad_l", C.c_int32),
+                ("fwd_kernel", C.c_int32), ("fwd_blocks", C.c_int32), ("dgrad_kernel", C.c_int32), ("dgrad_blocks", C.c_int32),
+                ("wgrad_ok", C.c_int32), ("wgrad_chunks", C.c_int32), ("wgrad_ppc", C.c_int32), ("bwd_blocks", C.c_int32),
+                ("stats_r", C.c_int32), ("stats_ppc", C.c_int32), ("stats_rows_per_sample", C.c_int32), ("stats_blocks", C.c_int32),
+                ("wgrad_workspace_bytes", C.c_uint64)]
+
+
+# enum rn_dw_fwd / rn_dw_dgrad
+DW_FWDS = {0: None, 1: "k3", 2: "generic"}
+DW_DGRADS = {0: None, 1: "k3_parity", 2: "k3", 3: "generic"}
+
+
 _lib = None
 
 # every symbol include/rn_hip.h declares (tests/test_abi.py checks the .so exports them all)
@@ -301,7 +315,7 @@ SYMBOLS = [
     "rn_winograd_bwd_products_workspace", "rn_winograd_bwd_products", "rn_wino_gn_rows", "rn_conv3x3_winograd_gn", "rn_conv3x3_winograd_gn_bwd", "rn_conv3x3_winograd_gn_bwd_wgrad", "rn_conv3x3_winograd_gn_plan", "rn_reduce_rows", "rn_resize_bilinear_normalize", "rn_resize_pair_u8",
     "rn_resize_pair_u8_augment_workspace", "rn_resize_pair_u8_augment",
     "rn_resize_pair_u8_batch", "rn_resize_pair_u8_augment_batch_workspace", "rn_resize_pair_u8_augment_batch",
-    "rn_depthwise_fwd", "rn_depthwise_dgrad", "rn_depthwise_wgrad_workspace", "rn_depthwise_wgrad", "rn_depthwise_bwd",
+    "rn_depthwise_fwd", "rn_depthwise_dgrad", "rn_depthwise_wgrad_workspace", "rn_depthwise_wgrad", "rn_depthwise_bwd", "rn_depthwise_plan",
     "rn_group_norm_sync_bytes", "rn_group_norm_workspace", "rn_group_norm_fwd", "rn_group_norm_bwd", "rn_group_norm_plan",
     "rn_act_fwd", "rn_act_bwd", "rn_upsample_add_fwd", "rn_upsample_add_bwd_top",
     "rn_pack_weights_f16", "rn_pack_weights_f16_bytes", "rn_cast_f32_to_f16", "rn_pad_cast_rgb_f16", "rn_conv2d_fwd_f16", "rn_conv2d_f16_fold_rows", "rn_conv2d_fwd_f16_fold", "rn_group_norm_finalize", "rn_group_norm_apply_f16", "rn_group_norm_apply_res_f16", "rn_maxpool_fwd_f16", "rn_maxpool_gn_fwd_f16", "rn_upsample_add_fwd_f16",
@@ -350,6 +364,7 @@ def lib():
         L.rn_depthwise_dgrad.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]
         L.rn_depthwise_bwd.argtypes = [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.rn_depthwise_wgrad_workspace.argtypes = [C.c_int] * 6
+        L.rn_depthwise_plan.argtypes = [C.c_int] * 7 + [C.POINTER(DwPlan)]
         L.rn_depthwise_wgrad.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.rn_conv2d_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rn_conv2d_dgrad.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

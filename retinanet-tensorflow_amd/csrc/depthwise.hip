@@ -294,73 +294,96 @@ int fill(DwArgs* a, int n, int h, int w, int c, int k, int stride) {
   return RN_OK;
 }
 
-unsigned grid_for(int64_t total) {
-  int64_t b = (total + T - 1) / T;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
-void wgrad_plan(const DwArgs& a, int* chunks, int* ppc) {
-  const int64_t npix = (int64_t)a.n * a.oh * a.ow;
-  int64_t ck = (npix * a.c + 2047) / 2048;   // short blocks: the tap loop is latency-bound
-  if (ck > 4096) ck = 4096;
-  if (ck < 1) ck = 1;
-  *ppc = (int)((npix + ck - 1) / ck);
-  *chunks = (int)((npix + *ppc - 1) / *ppc);
+// The ONE host decision of this file: every rn_depthwise_* entry point launches what this says, and rn_depthwise_plan reports
+// it.  Fills the geometry of `a` (pointers stay with the caller) and the plan; groups < 1: no statistics asked for.
+//   forward / dgrad   one thread per (pixel, channel quad), at most 8192 blocks (grid-stride loops); 3x3 has unrolled,
+//                     branch-free kernels, whose dgrad takes the 2 x 2 parity taps at stride 2
+//   weight gradient   pixel chunks of about 2048 elements (short blocks: the tap loop is latency-bound), at most 4096; 3x3 only
+//   statistics        R pixels per thread: 4, or 8 / 16 where that keeps a sample at <= 1024 rows (per-group rows: a thousand
+//                     are still cheap to merge; short blocks: a thread's pixels are a serial chain); 0 where the kernel's
+//                     index arithmetic (floor(p / ow) in fp32, fp32 per-group sums) or the GroupNorm's merge declines
+int decide(DwArgs* a, int n, int h, int w, int c, int k, int stride, int groups, rn_dw_plan* pl) {
+  *pl = rn_dw_plan{};
+  if (int e = fill(a, n, h, w, c, k, stride)) return e;
+  auto grid_for = [](int64_t total) {
+    int64_t b = (total + T - 1) / T;
+    if (b > 8192) b = 8192;
+    if (b < 1) b = 1;
+    return (int32_t)b;
+  };
+  pl->oh = a->oh; pl->ow = a->ow; pl->pad_t = a->pad_t; pl->pad_l = a->pad_l;
+  pl->fwd_kernel = k == 3 ? RN_DW_FWD_K3 : RN_DW_FWD_GENERIC;
+  pl->fwd_blocks = grid_for((int64_t)n * a->oh * a->ow * (c / 4));
+  pl->dgrad_kernel = k != 3 ? RN_DW_DGRAD_GENERIC : stride == 2 ? RN_DW_DGRAD_K3_PARITY : RN_DW_DGRAD_K3;
+  pl->dgrad_blocks = grid_for((int64_t)n * h * w * (c / 4));
+  {
+    const int64_t npix = (int64_t)n * a->oh * a->ow;
+    int64_t ck = (npix * c + 2047) / 2048;
+    if (ck > 4096) ck = 4096;
+    if (ck < 1) ck = 1;
+    pl->wgrad_ppc = (int32_t)((npix + ck - 1) / ck);
+    pl->wgrad_chunks = (int32_t)((npix + pl->wgrad_ppc - 1) / pl->wgrad_ppc);
+    pl->wgrad_workspace_bytes = (uint64_t)pl->wgrad_chunks * k * k * c * sizeof(float);
+    pl->wgrad_ok = k == 3;
+    pl->bwd_blocks = pl->wgrad_ok ? pl->dgrad_blocks + pl->wgrad_chunks : 0;
+  }
+  const long ohw = (long)a->oh * a->ow;
+  if (k == 3 && groups >= 1 && c % groups == 0 && ohw < (1 << 20) && a->ow <= 4096 && (double)ohw * (c / groups) < 16777216.0) {
+    const int lanes = ST / (c / 4);
+    int r = 4;
+    while (r < 16 && rn::ceil_div((int)ohw, lanes * r) > 1024) r *= 2;
+    const int cps = rn::ceil_div((int)ohw, lanes * r);
+    if (rn_group_norm_rows_ok(c, groups, cps, 1)) {
+      pl->stats_r = r; pl->stats_ppc = lanes * r; pl->stats_rows_per_sample = cps; pl->stats_blocks = n * cps;
+    }
+  }
+  return RN_OK;
 }
 
 }  // namespace
+
+extern "C" int rn_depthwise_plan(int n, int h, int w, int c, int k, int stride, int groups, rn_dw_plan* plan) {
+  RN_CHECK_ARG(plan, "depthwise plan: null plan");
+  DwArgs a = {};
+  return decide(&a, n, h, w, c, k, stride, groups, plan);
+}
 
 extern "C" int rn_depthwise_fwd(const float* x, const float* wgt, float* y, int n, int h, int w, int c, int k,
                                 int stride, rn_stream_t stream) {
   DwArgs a = {};
-  if (int e = fill(&a, n, h, w, c, k, stride)) return e;
+  rn_dw_plan pl;
+  if (int e = decide(&a, n, h, w, c, k, stride, 0, &pl)) return e;
   RN_CHECK_ARG(x && wgt && y, "depthwise fwd: null pointer");
   a.x = x; a.w = wgt; a.out = y;
-  if (k == 3) hipLaunchKernelGGL(dw_fwd_kernel<true>, dim3(grid_for((int64_t)n * a.oh * a.ow * (c / 4))), dim3(T), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(dw_fwd_kernel<false>, dim3(grid_for((int64_t)n * a.oh * a.ow * (c / 4))), dim3(T), 0, (hipStream_t)stream, a);
+  if (pl.fwd_kernel == RN_DW_FWD_K3) hipLaunchKernelGGL(dw_fwd_kernel<true>, dim3((unsigned)pl.fwd_blocks), dim3(T), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(dw_fwd_kernel<false>, dim3((unsigned)pl.fwd_blocks), dim3(T), 0, (hipStream_t)stream, a);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }
 
-namespace {
-// plan of the statistics kernel: pixels per thread R (4, or 8 / 16 where that keeps a sample at <= 1024 rows)
-bool stats_plan(const DwArgs& a, int groups, int* R, int* ppc, int* chunks_ps) {
-  if (a.k != 3 || groups < 1 || a.c % groups) return false;
-  const long ohw = (long)a.oh * a.ow;
-  if (ohw >= (1 << 20) || a.ow > 4096 || (double)ohw * (a.c / groups) >= 16777216.0) return false;
-  const int lanes = ST / (a.c / 4);
-  int r = 4;
-  while (r < 16 && rn::ceil_div((int)ohw, lanes * r) > 1024) r *= 2;  // (per-group rows: a thousand are still cheap to merge; short blocks: a thread's pixels are a serial chain)
-  *R = r; *ppc = lanes * r; *chunks_ps = rn::ceil_div((int)ohw, lanes * r);
-  return rn_group_norm_rows_ok(a.c, groups, *chunks_ps, 1) != 0;
-}
-}  // namespace
-
 extern "C" size_t rn_depthwise_stats_rows(int n, int h, int w, int c, int k, int stride, int groups, rn_gn_rows* layout) {
   DwArgs a = {};
+  rn_dw_plan pl;
   if (n < 1 || h < 1 || w < 1 || c < 4 || c % 4 || c > 1024 || k < 1 || stride < 1) return 0;
-  if (fill(&a, n, h, w, c, k, stride)) return 0;
-  int R, ppc, cps;
-  if (!stats_plan(a, groups, &R, &ppc, &cps)) return 0;
-  if (layout) { layout->rows_per_sample = cps; layout->per_group = 1; layout->groups = groups; }
-  return (size_t)n * cps * groups * 8;
+  if (decide(&a, n, h, w, c, k, stride, groups, &pl) || !pl.stats_r) return 0;
+  if (layout) { layout->rows_per_sample = pl.stats_rows_per_sample; layout->per_group = 1; layout->groups = groups; }
+  return (size_t)n * pl.stats_rows_per_sample * groups * 8;
 }
 
 extern "C" int rn_depthwise_fwd_stats(const float* x, const float* wgt, float* y, int n, int h, int w, int c, int k, int stride,
                                       const rn_gn_rows* rows, rn_stream_t stream) {
   DwStatArgs b = {};
-  if (int e = fill(&b.a, n, h, w, c, k, stride)) return e;
+  rn_dw_plan pl;
+  if (int e = decide(&b.a, n, h, w, c, k, stride, rows ? rows->groups : 0, &pl)) return e;
   RN_CHECK_ARG(x && wgt && y && rows && rows->rows, "depthwise fwd stats: null pointer");
-  int R;
-  RN_UNSUPPORTED(!stats_plan(b.a, rows->groups, &R, &b.ppc, &b.chunks_ps) || rows->rows_per_sample != b.chunks_ps || rows->per_group != 1,
+  RN_UNSUPPORTED(!pl.stats_r || rows->rows_per_sample != pl.stats_rows_per_sample || rows->per_group != 1,
                  "depthwise fwd stats: unsupported shape / layout (rn_depthwise_stats_rows)");
+  b.ppc = pl.stats_ppc; b.chunks_ps = pl.stats_rows_per_sample;
   b.a.x = x; b.a.w = wgt; b.a.out = y;
   b.st.rows = (float2*)rows->rows; b.st.groups = rows->groups; b.st.cpg = c / rows->groups;
-  const dim3 grid((unsigned)(n * b.chunks_ps));
-  if (R == 4) hipLaunchKernelGGL(dw_fwd_stats_kernel<4>, grid, dim3(ST), 0, (hipStream_t)stream, b);
-  else if (R == 8) hipLaunchKernelGGL(dw_fwd_stats_kernel<8>, grid, dim3(ST), 0, (hipStream_t)stream, b);
+  const dim3 grid((unsigned)pl.stats_blocks);
+  if (pl.stats_r == 4) hipLaunchKernelGGL(dw_fwd_stats_kernel<4>, grid, dim3(ST), 0, (hipStream_t)stream, b);
+  else if (pl.stats_r == 8) hipLaunchKernelGGL(dw_fwd_stats_kernel<8>, grid, dim3(ST), 0, (hipStream_t)stream, b);
   else hipLaunchKernelGGL(dw_fwd_stats_kernel<16>, grid, dim3(ST), 0, (hipStream_t)stream, b);
   RN_LAUNCH_CHECK();
   return RN_OK;
@@ -369,32 +392,33 @@ extern "C" int rn_depthwise_fwd_stats(const float* x, const float* wgt, float* y
 extern "C" int rn_depthwise_dgrad(const float* dy, const float* wgt, float* dx, int n, int h, int w, int c, int k,
                                   int stride, rn_stream_t stream) {
   DwArgs a = {};
-  if (int e = fill(&a, n, h, w, c, k, stride)) return e;
+  rn_dw_plan pl;
+  if (int e = decide(&a, n, h, w, c, k, stride, 0, &pl)) return e;
   RN_CHECK_ARG(dy && wgt && dx, "depthwise dgrad: null pointer");
   a.dy = dy; a.w = wgt; a.out = dx;
-  if (k == 3) hipLaunchKernelGGL(dw_dgrad_kernel<true>, dim3(grid_for((int64_t)n * h * w * (c / 4))), dim3(T), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(dw_dgrad_kernel<false>, dim3(grid_for((int64_t)n * h * w * (c / 4))), dim3(T), 0, (hipStream_t)stream, a);
+  if (pl.dgrad_kernel != RN_DW_DGRAD_GENERIC) hipLaunchKernelGGL(dw_dgrad_kernel<true>, dim3((unsigned)pl.dgrad_blocks), dim3(T), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(dw_dgrad_kernel<false>, dim3((unsigned)pl.dgrad_blocks), dim3(T), 0, (hipStream_t)stream, a);
   RN_LAUNCH_CHECK();
   return RN_OK;
 }
 
 extern "C" size_t rn_depthwise_wgrad_workspace(int n, int h, int w, int c, int k, int stride) {
   DwArgs a = {};
-  if (fill(&a, n, h, w, c, k, stride)) return 0;
-  int chunks, ppc;
-  wgrad_plan(a, &chunks, &ppc);
-  return (size_t)chunks * k * k * c * sizeof(float);
+  rn_dw_plan pl;
+  if (decide(&a, n, h, w, c, k, stride, 0, &pl)) return 0;
+  return (size_t)pl.wgrad_workspace_bytes;
 }
 
 extern "C" int rn_depthwise_wgrad(const float* x, const float* dy, float* dw, int n, int h, int w, int c, int k,
                                   int stride, void* workspace, size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer) {
   rn::DeferScope defer_scope_(defer);
   DwArgs a = {};
-  if (int e = fill(&a, n, h, w, c, k, stride)) return e;
+  rn_dw_plan pl;
+  if (int e = decide(&a, n, h, w, c, k, stride, 0, &pl)) return e;
   RN_CHECK_ARG(x && dy && dw && workspace, "depthwise wgrad: null pointer");
-  RN_UNSUPPORTED(k != 3, "depthwise wgrad: only 3x3 kernels (got %d)", k);
-  wgrad_plan(a, &a.chunks, &a.ppc);
-  const size_t need = (size_t)a.chunks * 9 * c * sizeof(float);
+  RN_UNSUPPORTED(!pl.wgrad_ok, "depthwise wgrad: only 3x3 kernels (got %d)", k);
+  a.chunks = pl.wgrad_chunks; a.ppc = pl.wgrad_ppc;
+  const size_t need = (size_t)pl.wgrad_workspace_bytes;
   if (workspace_bytes < need) {
     rn::set_error("depthwise wgrad: workspace %zu < %zu", workspace_bytes, need);
     return RN_EWORKSPACE;
@@ -412,21 +436,22 @@ extern "C" int rn_depthwise_bwd(const float* x, const float* dy, const float* wg
                                 int k, int stride, void* workspace, size_t workspace_bytes, rn_stream_t stream, rn_reduce_list* defer) {
   rn::DeferScope defer_scope_(defer);
   DwBwdArgs b = {};
-  if (int e = fill(&b.d, n, h, w, c, k, stride)) return e;
+  rn_dw_plan pl;
+  if (int e = decide(&b.d, n, h, w, c, k, stride, 0, &pl)) return e;
   RN_CHECK_ARG(x && dy && wgt && dx && dw && workspace, "depthwise bwd: null pointer");
-  RN_UNSUPPORTED(k != 3, "depthwise bwd: only 3x3 kernels (got %d)", k);
+  RN_UNSUPPORTED(!pl.wgrad_ok, "depthwise bwd: only 3x3 kernels (got %d)", k);
   b.w = b.d;
-  wgrad_plan(b.w, &b.w.chunks, &b.w.ppc);
-  const size_t need = (size_t)b.w.chunks * 9 * c * sizeof(float);
+  b.w.chunks = pl.wgrad_chunks; b.w.ppc = pl.wgrad_ppc;
+  const size_t need = (size_t)pl.wgrad_workspace_bytes;
   if (workspace_bytes < need) {
     rn::set_error("depthwise bwd: workspace %zu < %zu", workspace_bytes, need);
     return RN_EWORKSPACE;
   }
   b.d.dy = dy; b.d.w = wgt; b.d.out = dx;
   b.w.x = x; b.w.dy = dy; b.w.partial = (float*)workspace;
-  b.dgrad_blocks = (int)grid_for((int64_t)n * h * w * (c / 4));
+  b.dgrad_blocks = pl.dgrad_blocks;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(dw_bwd_kernel, dim3(b.dgrad_blocks + b.w.chunks), dim3(T), 0, st, b);
+  hipLaunchKernelGGL(dw_bwd_kernel, dim3((unsigned)pl.bwd_blocks), dim3(T), 0, st, b);
   RN_LAUNCH_CHECK();
   return rn::launch_reduce_rows((const float*)workspace, dw, 9 * c, b.w.chunks, 0, st);
 }
