@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 425
+#define RN_API_VERSION 426
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -469,6 +469,52 @@ typedef struct rn_dw_plan {
   uint64_t wgrad_workspace_bytes;       /* = rn_depthwise_wgrad_workspace                                                   */
 } rn_dw_plan;
 int rn_depthwise_plan(int n, int h, int w, int c, int k, int stride, int groups, rn_dw_plan* plan);
+
+/* ------------------------------------------------------------------ fp16 inference depthwise 3x3
+ * The DepthwiseConv2D of MobileNetV2's bottleneck at inference (mobilenet_v2.py:15-38, tf.nn.depthwise_conv2d at :35-36; built
+ * into the block at :66-68 between the Normalization + activation of the expand conv, :57-61, and its own, :69-70;
+ * normalization.py:20-35): x, y fp16 NHWC, wgt the fp32 kernel [3,3,c] as the parameter is stored (9 c floats, no packing), fp32
+ * accumulation, stride 1 or 2, TF SAME padding, c a multiple of 8 (at most 2048).
+ *   input side (in_mean .. in_beta all non-NULL; all NULL and in_groups = in_act = 0: x is a finished activation): rn_f16_fold's
+ *     semantics -- x is the RAW fp16 output of the conv in front; the kernel loads act(GN(x)), formed in fp32 and rounded to fp16
+ *     exactly as rn_group_norm_apply_f16 would have stored it, and pads with zeros AFTER the activation.  in_mean / in_rstd
+ *     [n][in_groups], in_gamma / in_beta [c]; any channels per group (an octet of channels may straddle groups).
+ *   output side (partial != NULL): sums of y and y^2, of the values as stored in fp16, per (pixel chunk, channel) in the layout
+ *     [2][n * rows][c], rows = rn_depthwise_f16_rows(n, h, w, c, stride) chunks per sample (a chunk never straddles samples): what
+ *     rn_group_norm_finalize reads.  Fixed-order reduction through LDS, no atomics.
+ * Checked before any launch.  RN_EINVAL: a NULL descriptor, x, wgt or y; in_* given partly (or in_groups / in_act without them);
+ * c % 8 != 0; stride outside {1, 2}; x, wgt, y or partial not 16-byte aligned, an in_* pointer not 4-byte aligned.
+ * RN_EUNSUPPORTED: k != 3, c > 2048, 2^31 elements and more. */
+typedef struct rn_dw_f16 {
+  const void* x; const float* wgt; void* y;
+  int32_t n, h, w, c, k, stride;
+  const float* in_mean; const float* in_rstd; const float* in_gamma; const float* in_beta;
+  int32_t in_groups, in_act;
+  float* partial;
+} rn_dw_f16;
+int rn_depthwise_f16_rows(int n, int h, int w, int c, int stride);       /* 0: a shape rn_depthwise_fwd_f16 refuses */
+int rn_depthwise_fwd_f16(const rn_dw_f16* d, rn_stream_t stream);
+/* What rn_depthwise_fwd_f16 launches for the same descriptor: the launch decision stopped before the launch (one function).
+ * Host only: touches no device; the descriptor's pointers are compared with NULL and checked for alignment, never followed.
+ * Returns what the launch would return (a refused call's plan is zeroed), RN_EINVAL for a NULL plan.
+ * A block of 256 threads is pixel_lanes x (c / 8) threads (the rest idle); a thread owns one channel octet and computes one strip
+ * of pixels_per_thread outputs along w by rows_per_thread output rows; a block is one chunk = one statistic row. */
+enum rn_dw_f16_kernel { RN_DW_F16_S1 = 1 /* dw_f16_kernel<1, P, ..> */, RN_DW_F16_S2 = 2 /* dw_f16_kernel<2, P, ..> */ };
+typedef struct rn_dw_f16_plan {
+  int32_t oh, ow, pad_t, pad_l;      /* SAME geometry                                                                  */
+  int32_t kernel;                    /* enum rn_dw_f16_kernel                                                          */
+  int32_t pixels_per_thread;         /* P, the strip's width: 4 at stride 1, 2 at stride 2; 1 where ow is smaller     */
+  int32_t pixel_lanes;               /* 256 / (c / 8)                                                                  */
+  int32_t rows_per_thread;           /* R, the strip's height: 4 (oh >= 32), 2 (oh >= 8), 1                            */
+  int32_t strips_per_sample;         /* ceil(oh / R) * ceil(ow / P)                                                    */
+  int32_t strips_per_chunk;          /* = pixel_lanes                                                                  */
+  int32_t pixels_per_chunk;          /* strips_per_chunk * P * R (strips at the right / bottom edge may hold fewer)    */
+  int32_t rows_per_sample;           /* = rn_depthwise_f16_rows                                                        */
+  int32_t blocks;                    /* n * rows_per_sample (not capped)                                               */
+  int32_t fold;                      /* the input side is applied                                                      */
+  int32_t stats;                     /* statistic rows are written                                                     */
+} rn_dw_f16_plan;
+int rn_depthwise_f16_plan(const rn_dw_f16* d, rn_dw_f16_plan* plan);
 
 /* ------------------------------------------------------------------ GroupNorm (+act, +dropout, +residual)
  * Replaces normalization.py:20-35 (reshape + tf.nn.moments + affine), the activation that

@@ -22,7 +22,7 @@ LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
 CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
-API_VERSION = 425       # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 426      # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -199,6 +199,24 @@ F16_KERNELS = {0: None, 1: "igemm", 2: "sg"}
 F16_EPILOGUES = {0: "staged", 1: "scalar_f16", 2: "scalar_f32"}
 
 
+class DwF16(C.Structure):
+    """rn_dw_f16: one fp16 depthwise 3 x 3 call (rn_depthwise_fwd_f16)"""
+    _fields_ = [("x", C.c_void_p), ("wgt", C.c_void_p), ("y", C.c_void_p),
+                ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32),
+                ("in_mean", C.c_void_p), ("in_rstd", C.c_void_p), ("in_gamma", C.c_void_p), ("in_beta", C.c_void_p),
+                ("in_groups", C.c_int32), ("in_act", C.c_int32), ("partial", C.c_void_p)]
+
+
+class DwF16Plan(C.Structure):
+    """rn_dw_f16_plan: what rn_depthwise_fwd_f16 launches for a descriptor (rn_depthwise_f16_plan, host only)"""
+    _fields_ = [(name, C.c_int32) for name in (
+        "oh", "ow", "pad_t", "pad_l", "kernel", "pixels_per_thread", "pixel_lanes", "rows_per_thread", "strips_per_sample",
+        "strips_per_chunk", "pixels_per_chunk", "rows_per_sample", "blocks", "fold", "stats")]
+
+
+DW_F16_KERNELS = {0: None, 1: "s1", 2: "s2"}       # enum rn_dw_f16_kernel
+
+
 class MbRows(C.Structure):
     """rn_mb_rows"""
     _fields_ = [("rows", C.c_void_p), ("rows_per_sample", C.c_int32), ("width", C.c_int32), ("bn", C.c_int32)]
@@ -335,6 +353,7 @@ SYMBOLS = [
     "rn_debug_collective_standin", "rn_optimizer_norm_pairs", "rn_norm_reg_finalize",
     "rn_step_control_eval", "rn_grad_norm_partial",
     "rn_train_metrics_workspace", "rn_train_metrics_pass", "rn_train_metrics_fold", "rn_train_metrics_reset",
+    "rn_depthwise_f16_rows", "rn_depthwise_fwd_f16", "rn_depthwise_f16_plan",
 ]
 
 
@@ -464,6 +483,9 @@ def lib():
         L.rn_conv2d_fwd_f16.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.rn_conv2d_f16_fold_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rn_conv2d_fwd_f16_fold.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rn_depthwise_f16_rows.argtypes = [C.c_int] * 5
+        L.rn_depthwise_fwd_f16.argtypes = [C.POINTER(DwF16), C.c_void_p]
+        L.rn_depthwise_f16_plan.argtypes = [C.POINTER(DwF16), C.POINTER(DwF16Plan)]
         L.rn_group_norm_finalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rn_group_norm_apply_f16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]

@@ -182,6 +182,8 @@ class DepthwiseConv2D(torch.nn.Module):
     def forward(self, input, norm=None):
         if self.weight is None:
             self.build(input.shape[3], input.device)
+        if input.dtype == torch.float16:        # fp16 inference (INFERENCE_F16): forward only
+            return ops_f16.depthwise(input, self.weight, self.strides)
         return ops.depthwise_conv2d(input, self.weight, self.strides, gn=(norm.groups, norm.eps) if norm is not None else None)
 
 

@@ -43,6 +43,23 @@ MB_CHAIN = os.environ.get("RN_MB_CHAIN", "1") == "1"
 # bottleneck_2_2 on).
 MB_CHAIN_MAX_HW = int(os.environ.get("RN_MB_CHAIN_MAX_HW", 0))
 STAGE_CUT_AFTER = 'bottleneck_3_3'      # (the C3 tap: everything above it is 95 % of the backbone's gradient bytes and runs on maps <= 32 x 32)
+# fp16 inference (layers.set_inference_dtype('f16')).  1: the backbone itself runs in fp16 -- every bottleneck's GroupNorms folded
+# into the convs around them (Bottleneck._call_f16_folded; csrc/depthwise_f16.hip is the depthwise conv).  0 (the default: measured
+# faster, 1069 - 1076 vs 955 - 956 images/s at 1024 x 1024 batch 16, profiles/mb_f16_inference.txt): the backbone runs in fp32
+# through the fused chain above and only C3, C4, C5 are cast to fp16 for the FPN and the heads.
+F16_BACKBONE = os.environ.get("RN_F16_MB_BACKBONE", "0") == "1"
+
+
+def _f16_conv_norm(x, conv, norm, act, residual=None):
+    """1 x 1 / stem conv -> GroupNorm -> act on the fp16 path.  x: fp16 tensor or ops_f16.Pending.  A Pending where the conv can
+    fold (ops_f16.conv2d_norm); else the finished fp16 tensor from conv + three-kernel GroupNorm, `residual` added."""
+    import ops_f16
+    p = ops_f16.conv2d_norm(x, conv.weight, norm, act, conv.strides, conv.groups) if ops_f16.FOLD else None
+    if p is not None:
+        return p
+    t = x.materialise() if isinstance(x, ops_f16.Pending) else x
+    return ops_f16.group_norm_act(ops_f16.conv2d(t, conv.weight, None, conv.strides, conv.groups), norm.gamma, norm.beta, norm.groups,
+                                  norm.eps, act, residual)
 
 
 class DepthwiseConv2D(L.DepthwiseConv2D):
@@ -79,10 +96,38 @@ class Bottleneck(Model):
             self.build(input.shape[3])
             self.to(input.device)
         identity = None
-        if self._same_shape:        # the input feeds the expand conv and the residual: their gradients are summed by our kernel
+        if input.dtype == torch.float16 and not training:
+            import ops_f16
+            if ops_f16.FOLD:
+                return self._call_f16_folded(input)
+        if self._same_shape and input.dtype == torch.float16:       # fp16 inference, layer by layer: no gradients to sum
+            identity = input
+        elif self._same_shape:      # the input feeds the expand conv and the residual: their gradients are summed by our kernel
             input, identity = ops.fanout(input, 2)
         mid = self.depthwise_conv(self.expand_conv(input, training), training)
         return self.linear_conv(mid, training, residual=identity)
+
+    def _call_f16_folded(self, input, keep_pending=False):
+        """fp16 inference with the block's three GroupNorms folded into its convs (the pattern of
+        resnet.ResNeXt_Bottleneck._call_f16_folded): the expand conv's epilogue emits the statistics of its output, the depthwise
+        conv applies that GroupNorm + activation on its operand load and emits its own statistics (ops_f16.depthwise_norm), the
+        linear conv does the same.  `input`: an fp16 tensor, or the Pending output of the block in front (a block without a
+        residual).  The block's output is materialised once -- with the residual in the same pass -- unless `keep_pending` and
+        there is no residual: then the Pending goes to the next block's expand conv.  A 1 x 1 conv whose map is not a whole number
+        of m-tiles runs conv + GroupNorm layer by layer (_f16_conv_norm); the depthwise conv folds at every shape."""
+        import ops_f16
+        conv1, norm1, act1, _ = self.expand_conv.layers
+        dw, norm2, act2, _ = self.depthwise_conv.layers
+        conv3, norm3, _ = self.linear_conv.layers
+        if self._same_shape and isinstance(input, ops_f16.Pending):
+            input = input.materialise()                 # read twice: by the expand conv and as the residual
+        identity = input if self._same_shape else None
+        a1 = _f16_conv_norm(input, conv1, norm1, L.activation_name(act1))
+        p2 = ops_f16.depthwise_norm(a1, dw.weight, norm2, L.activation_name(act2), dw.strides)
+        a3 = _f16_conv_norm(p2, conv3, norm3, None, residual=identity)
+        if isinstance(a3, ops_f16.Pending) and not (keep_pending and identity is None):
+            return a3.materialise(residual=identity)
+        return a3
 
 
 class MobileNetV2(Model):
@@ -165,7 +210,48 @@ class MobileNetV2(Model):
             cache[key] = start
         return cache[key]
 
+    def _call_f16(self, image):
+        """The backbone in fp16 (F16_BACKBONE): stem on the 4-channel fp16 image, then every bottleneck folded; a Pending travels
+        from a block to the next one's expand conv unless the block has a residual or its output is a tap of the pyramid.  C1
+        (which no caller of an inference pass reads) is not materialised: the key is present, as in resnet.ResNeXt.call.
+        ops_f16.FOLD off: every layer on its own (conv / depthwise, then the three-kernel GroupNorm)."""
+        import ops_f16
+        out = {}
+        x = ops_f16.image_to_half4(image)
+        if not ops_f16.FOLD:
+            x = self.input_conv(x, False)
+            for name in self.block_names:
+                x = getattr(self, name)(x, False)
+                if name in _TAP_AFTER:
+                    out[_TAP_AFTER[name]] = x
+            out['C5'] = self.output_conv(x, False)
+            return out
+        conv_s, norm_s, act_s, _ = self.input_conv.layers
+        x = _f16_conv_norm(x, conv_s, norm_s, L.activation_name(act_s))
+        for name in self.block_names:
+            tap = _TAP_AFTER.get(name)
+            x = getattr(self, name)._call_f16_folded(x, keep_pending=tap not in ('C3', 'C4'))
+            if tap is not None:
+                out[tap] = None if isinstance(x, ops_f16.Pending) else x
+        conv_o, norm_o, act_o, _ = self.output_conv.layers
+        c5 = _f16_conv_norm(x, conv_o, norm_o, L.activation_name(act_o))
+        out['C5'] = c5.materialise() if isinstance(c5, ops_f16.Pending) else c5
+        return out
+
     def call(self, input, training):
+        if L.INFERENCE_F16 and not training and torch.is_tensor(input) and input.is_cuda and input.dtype == torch.float32:
+            if F16_BACKBONE:
+                return self._call_f16(input)
+            # the backbone in fp32 (the fused chain), its taps cast for the fp16 FPN and heads
+            import ops_f16
+            L.INFERENCE_F16 = False
+            try:
+                out = self.call(input, training)
+            finally:
+                L.INFERENCE_F16 = True
+            for k in ('C3', 'C4', 'C5'):
+                out[k] = ops_f16.to_half(out[k])
+            return out
         out = {}
         input = self.input_conv(input, training)
         start = self._chain_start(input, training)

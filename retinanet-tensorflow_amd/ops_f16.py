@@ -215,6 +215,54 @@ def conv2d_norm(x, w, norm, act=None, stride=1, groups=1):
     return Pending(y, mean, rstd, norm.gamma.detach(), norm.beta.detach(), gout, act)
 
 
+def _depthwise_call(x, w, stride, stats):
+    """One rn_depthwise_fwd_f16 launch.  x: fp16 NHWC tensor or a Pending (its GroupNorm + activation are applied on the operand
+    load); w: the fp32 parameter [3,3,c,1].  -> (y, partial [2, n rows, c] or None, rows per sample)"""
+    src = x.y if isinstance(x, Pending) else x.contiguous()
+    assert src.dtype == torch.float16 and w.dtype == torch.float32 and w.shape[2] == src.shape[3] and w.shape[3] == 1
+    n, h, wd, c = src.shape
+    k = w.shape[0]
+    wgt = w.detach().contiguous()
+    oh, _ = _rn.same_pad(h, k, stride)
+    ow, _ = _rn.same_pad(wd, k, stride)
+    y = torch.empty((n, oh, ow, c), dtype=torch.float16, device=src.device)
+    d = _rn.DwF16()
+    d.x, d.wgt, d.y = src.data_ptr(), wgt.data_ptr(), y.data_ptr()
+    d.n, d.h, d.w, d.c, d.k, d.stride = n, h, wd, c, k, stride
+    if isinstance(x, Pending):
+        d.in_mean, d.in_rstd, d.in_gamma, d.in_beta = x.mean.data_ptr(), x.rstd.data_ptr(), x.gamma.data_ptr(), x.beta.data_ptr()
+        d.in_groups, d.in_act = x.groups, _rn.ACT[x.act]
+    partial, rows = None, 0
+    if stats:
+        rows = _rn.lib().rn_depthwise_f16_rows(n, h, wd, c, stride)
+        if rows <= 0:
+            raise _rn.RnError("rn_depthwise_f16_rows: %s" % _rn.lib().rn_last_error().decode())
+        partial = torch.empty((2, n * rows, c), dtype=torch.float32, device=src.device)
+        d.partial = partial.data_ptr()
+    _rn.check(_rn.lib().rn_depthwise_fwd_f16(C.byref(d), _rn.stream()), "rn_depthwise_fwd_f16")
+    return y, partial, rows
+
+
+def depthwise(x, w, stride=1):
+    """fp16 depthwise 3 x 3 (mobilenet_v2.py:15-38), SAME padding: x fp16 NHWC, w the fp32 parameter [3,3,c,1] -> fp16 NHWC."""
+    return _depthwise_call(x, w, stride, False)[0]
+
+
+def depthwise_norm(x, w, norm, act=None, stride=1):
+    """depthwise 3 x 3 -> GroupNorm `norm` -> act with the GroupNorm NOT applied: a Pending (kernel with the statistics of its
+    output, then finalise).  `x`: an fp16 tensor or a Pending.  Every shape the kernel takes folds: never None."""
+    y, partial, rows = _depthwise_call(x, w, stride, True)
+    n, oh, ow, c = y.shape
+    if norm.gamma is None:
+        norm.build(c, y.device)
+    g = gn_groups(c, norm.groups)
+    mean = torch.empty((n, g), dtype=torch.float32, device=y.device)
+    rstd = torch.empty((n, g), dtype=torch.float32, device=y.device)
+    _rn.check(_rn.lib().rn_group_norm_finalize(_rn.f32(partial), n, rows, oh * ow, c, g, float(norm.eps), _rn.f32(mean), _rn.f32(rstd),
+                                               _rn.stream()), "rn_group_norm_finalize")
+    return Pending(y, mean, rstd, norm.gamma.detach(), norm.beta.detach(), g, act)
+
+
 HEAD_EPILOGUE_STATS = os.environ.get("RN_F16_HEAD_EPILOGUE_STATS", "1") == "1"
 
 

@@ -1239,9 +1239,20 @@ def _copy_tree(dst, src):
 # Minimal driver with the reference's flags (train.py:88-108).  --dataset pascal ROOT SUBSET / coco ANN IMAGES read the
 # annotation files (data_loaders/pascal.py, coco.py; JPEG decode with Pillow on the host); 'shapes' is a synthetic stand-in
 # following data_loaders/shapes.py:133-176 (1-4 filled squares, half-size in [20, S/4], 3 classes), rendered with numpy.
-def evaluate(net, data_loader, levels, num_images, scale=None, device='cuda', score_threshold=0.5):
+def evaluate(net, data_loader, levels, num_images, scale=None, device='cuda', score_threshold=0.5, dtype='f32'):
     """Inference + decode + class-wise NMS (train.py:68-85) over `num_images` samples of the loader, scored with
-    COCO-style mAP and the reference's two IoU metrics (train.py:137-161); see metrics.py."""
+    COCO-style mAP and the reference's two IoU metrics (train.py:137-161); see metrics.py.
+    dtype 'f16': the forward passes run in fp16 storage (layers.set_inference_dtype; logits and box deltas leave the net in fp32);
+    the setting in force before the call is restored afterwards, also when the call raises."""
+    if dtype != 'f32':
+        import layers
+        assert dtype == 'f16', dtype
+        before = (layers.INFERENCE_F16, layers.F16_OUTPUTS_F32)
+        layers.set_inference_dtype('f16', outputs='f32')
+        try:
+            return evaluate(net, data_loader, levels, num_images, scale, device, score_threshold)
+        finally:
+            layers.INFERENCE_F16, layers.F16_OUTPUTS_F32 = before
     import dataset
     import metrics
     dets, gts, ciou, riou = [], [], [], []
@@ -1308,6 +1319,8 @@ def build_parser():
                         help='file datasets: runs of <= K samples of one network input size (default 8; 0 = plain shuffle)')
     parser.add_argument('--decode-workers', type=int, default=4, help='threads decoding the image files (at most 16)')
     parser.add_argument('--eval-images', type=int, default=0, help='after training: mAP / IoU metrics over this many samples')
+    parser.add_argument('--eval-fp16', action='store_true',
+                        help='with --eval-images: evaluate once more with fp16 inference and print an `eval (fp16):` line')
     parser.add_argument('--eval-dataset', type=str, nargs='+', default=None,
                         help='TYPE ARGS... as --dataset; required with --eval-images for a file dataset')
     parser.add_argument('--augment', action='store_true',
@@ -1696,6 +1709,14 @@ def main(argv=None):
             with trainer.ema_weights():
                 res = evaluate(net, eval_loader, levels, args.eval_images, scale=args.scale, device=dev)
             print('eval (ema): mAP %.4f AP50 %.4f AP75 %.4f class_iou %.4f regr_iou %.4f over %d images' % (
+                res['mAP'], res['AP50'], res['AP75'], res['class_iou'], res['regr_iou'], res['images']), flush=True)
+        if args.eval_fp16:
+            if args.eval_dataset:
+                eval_loader = Inferred(args.eval_dataset[0], args.eval_dataset[1:])        # (a fresh loader: the same samples again)
+            else:
+                eval_loader = Shapes(None, image_size=(args.scale + args.scale // 4, args.scale), seed=12345)
+            res = evaluate(net, eval_loader, levels, args.eval_images, scale=args.scale, device=dev, dtype='f16')
+            print('eval (fp16): mAP %.4f AP50 %.4f AP75 %.4f class_iou %.4f regr_iou %.4f over %d images' % (
                 res['mAP'], res['AP50'], res['AP75'], res['class_iou'], res['regr_iou'], res['images']), flush=True)
     if started:
         import torch.distributed as dist

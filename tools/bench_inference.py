@@ -1,5 +1,8 @@
 """BASELINE configs[4] on one GPU: ResNeXt-50-FPN 1024x1024, batch 16, forward (training=False) + sigmoid (inside the candidate scan) +
-anchor decode + batched class-wise NMS, in fp32 and in fp16 storage (f16 matrix-core convs, fp32 accumulate)."""
+anchor decode + batched class-wise NMS, in fp32 and in fp16 storage (f16 matrix-core convs, fp32 accumulate).
+    python tools/bench_inference.py [backbone [size [batch [iters [rounds]]]]]
+With mobilenet_v2 the fp16 pass runs for both values of RN_F16_MB_BACKBONE (mobilenet_v2.F16_BACKBONE: 1 the backbone in fp16,
+0 the backbone in fp32 with its taps cast); `rounds` repeats the whole set interleaved (f32, f16 ..., f32, f16 ...) in one process."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "retinanet-tensorflow_amd")):
@@ -7,7 +10,7 @@ for p in (ROOT, os.path.join(ROOT, "retinanet-tensorflow_amd")):
 import torch
 
 
-def main(backbone="resnet_50", size=1024, batch=16, iters=5):
+def main(backbone="resnet_50", size=1024, batch=16, iters=5, rounds=1):
     import layers, levels, ops, retinanet, utils
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -25,8 +28,14 @@ def main(backbone="resnet_50", size=1024, batch=16, iters=5):
             return utils.detect_raw(out["classifications"], out["regressions"], anchors, 80, score_threshold=0.0105,
                                     capacity=int(rows * 0.5), return_raw=True, logits=True)
 
-    for dtype in ("f32", "f16"):
+    passes = [("f32", None), ("f16", None)]
+    if backbone == "mobilenet_v2":
+        import mobilenet_v2
+        passes = [("f32", None), ("f16", 1), ("f16", 0)]
+    for rnd, (dtype, mb_switch) in [(r, p) for r in range(rounds) for p in passes]:
         layers.set_inference_dtype(dtype)
+        if mb_switch is not None:
+            mobilenet_v2.F16_BACKBONE = bool(mb_switch)
         o = run(); torch.cuda.synchronize()
         counts = o[5].cpu().tolist()
         t0 = time.perf_counter()
@@ -51,13 +60,15 @@ def main(backbone="resnet_50", size=1024, batch=16, iters=5):
                 del g, og
             except Exception as e:       # (reported, not fatal: the eager figure stands)
                 graph_ips = "failed: %s" % (str(e)[:120],)
-        print(json.dumps({"backbone": backbone, "image_size": size, "batch": batch, "dtype": dtype,
+        print(json.dumps({"backbone": backbone, "image_size": size, "batch": batch, "dtype": dtype, "round": rnd,
+                          "RN_F16_MB_BACKBONE": mb_switch,
                           "images_per_sec": round(batch / el, 2), "ms_per_batch": round(el * 1e3, 2),
                           "images_per_sec_graph": graph_ips,
-                          "candidates": counts[0], "kept": counts[1], "conv_TFLOPs": round(596.0 * batch / el / 1e3, 1),
+                          "candidates": counts[0], "kept": counts[1], "conv_TFLOPs": round(596.0 * batch / el / 1e3, 1) if (backbone, size) == ("resnet_50", 1024) else None,
                           "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}), flush=True)
     layers.set_inference_dtype("f32")
 
 
 if __name__ == "__main__":
-    main()
+    a = sys.argv[1:]
+    main(a[0] if a else "resnet_50", *[int(v) for v in a[1:5]])

@@ -1,7 +1,8 @@
 """fp16 inference judged on a TRAINED net: ResNeXt-50-FPN trained on the shapes stream at 256^2 with the
 product's loop, then -- on held-out images -- the fp16 product's detections against the fp32 product's: survivors shared, score
 and box differences, mAP of both.  (The test adds the CPU oracle: tests/test_gpu_fullsize.py.)
-    python tools/f16_trained_probe.py [steps] [lr]"""
+    python tools/f16_trained_probe.py [steps] [lr] [backbone] [RN_F16_MB_BACKBONE]
+backbone: resnet_50 (default) or mobilenet_v2; for mobilenet_v2 the last argument (1 / 0) sets mobilenet_v2.F16_BACKBONE."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "retinanet-tensorflow_amd"), os.path.join(ROOT, "tests")):
@@ -53,13 +54,16 @@ def agreement(a, b):
     return shared / len(as_), shared / len(bs), ds, db
 
 
-def main(steps=2500, lr=1e-2, images=32):
+def main(steps=2500, lr=1e-2, images=32, backbone='resnet_50', mb_switch=None):
     import dataset, metrics, train
     from data_loaders.shapes import Shapes
     from test_gpu_train_cli import _shapes_trainer
     dev = torch.device("cuda:0")
-    net, tr, feed, lv = _shapes_trainer(dev, True, True, dropout=0.0, seed=0, scale=256, backbone='resnet_50')
+    net, tr, feed, lv = _shapes_trainer(dev, True, True, dropout=0.0, seed=0, scale=256, backbone=backbone)
     tr.opt.lr = lr
+    if backbone == 'mobilenet_v2' and mb_switch is not None:
+        import mobilenet_v2
+        mobilenet_v2.F16_BACKBONE = bool(int(mb_switch))
     t0 = time.perf_counter()
     for i in range(steps):
         out = tr.step()
@@ -81,7 +85,7 @@ def main(steps=2500, lr=1e-2, images=32):
     m32 = metrics.mean_average_precision(d32, gts, loader.num_classes)
     m16 = metrics.mean_average_precision(d16, gts, loader.num_classes)
     ag = np.array(ag)
-    print(json.dumps({"steps": steps, "lr": lr, "mAP_f32": round(m32["mAP"], 4), "mAP_f16": round(m16["mAP"], 4), "AP50_f32": round(m32["AP50"], 4),
+    print(json.dumps({"backbone": backbone, "RN_F16_MB_BACKBONE": mb_switch, "steps": steps, "lr": lr, "mAP_f32": round(m32["mAP"], 4), "mAP_f16": round(m16["mAP"], 4), "AP50_f32": round(m32["AP50"], 4),
                       "AP50_f16": round(m16["AP50"], 4), "survivors_f32": int(sum(len(d[1]) for d in d32)), "survivors_f16": int(sum(len(d[1]) for d in d16)),
                       "shared_of_f32_min": round(float(ag[:, 0].min()), 4), "shared_of_f32_mean": round(float(ag[:, 0].mean()), 4),
                       "shared_of_f16_mean": round(float(ag[:, 1].mean()), 4), "max_score_diff": round(float(ag[:, 2].max()), 5),
@@ -89,4 +93,5 @@ def main(steps=2500, lr=1e-2, images=32):
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 2500, float(sys.argv[2]) if len(sys.argv) > 2 else 1e-2)
+    main(int(sys.argv[1]) if len(sys.argv) > 1 else 2500, float(sys.argv[2]) if len(sys.argv) > 2 else 1e-2,
+         backbone=sys.argv[3] if len(sys.argv) > 3 else 'resnet_50', mb_switch=sys.argv[4] if len(sys.argv) > 4 else None)
