@@ -48,7 +48,7 @@ typedef struct rn_reduce_list rn_reduce_list;
 
 /* Version of this header's ABI: bumped whenever an entry point's arguments or a struct layout change.  rn_version() returns
  * the value the library was built with; a caller built against another value must not call anything else. */
-#define RN_API_VERSION 426
+#define RN_API_VERSION 427
 int rn_version(void);
 const char* rn_last_error(void);
 
@@ -516,6 +516,45 @@ typedef struct rn_dw_f16_plan {
 } rn_dw_f16_plan;
 int rn_depthwise_f16_plan(const rn_dw_f16* d, rn_dw_f16_plan* plan);
 
+/* ------------------------------------------------------------------ fp16 inference dense block (DenseNet-BC)
+ * The reference's dense block (densenet.py:117-121: output = composite_function(input); input = concat([input, output]))
+ * on ONE fp16 buffer [n, hw, ld], ld = c_in + depth * k, for inference: no concat, and the GroupNorm in front of every layer's
+ * 1 x 1 conv (densenet.py:61-66, normalization.py:20-35) takes its statistics from per-channel sums that are formed ONCE, when a
+ * channel slice is written -- the statistics of a channel prefix do not change inside a block.
+ *   rn_dense_f16_put       buf[:, :, coff : coff + c] = src (dense fp16 [n, hw, c]); in the same pass partial[0 | 1][sample][row][coff + j]
+ *                          = sum of x | x^2 (of the values as stored, fp32, fixed order) over the pixels of chunk `row` of the sample.
+ *                          partial is the caller's table [2][n][rows][ld] (fp32), rows = rn_dense_f16_rows(hw): a function of hw
+ *                          alone, so every slice of a block shares the layout.  Bytes of buf and partial outside the slice are not
+ *                          touched.  src == buf (with ld == c, coff == 0) asks for the sums of a finished tensor: nothing is stored to buf.
+ *   rn_dense_f16_finalize  mean / rstd [n][groups] of the prefix [0, c) from the table (fp64, fixed order); c / groups is any size
+ *                          (2, 3, 4 ... 51 in DenseNet-121 / -169 with groups = 32).
+ *   rn_dense_f16_norm      y (dense fp16 [n, hw, c]) = act(GN(buf[:, :, 0 : c])), formed in fp32 and rounded to fp16 exactly as
+ *                          rn_group_norm_apply_f16 stores it; c <= 2048.  A launch of its own behind the finalise.
+ * Checked before any launch.  RN_EINVAL: a NULL or misaligned (16 bytes) pointer, a shape < 1, ld < coff + c, coff != 0 or groups
+ * not dividing c for finalize / norm, an unknown act.  RN_EUNSUPPORTED: c, ld or coff not a multiple of 8, c > 2048 (norm),
+ * n > 65535. */
+int rn_dense_f16_rows(int hw);      /* statistic rows per sample; 0 for hw < 1 */
+int rn_dense_f16_put(const void* src, void* buf, float* partial, int n, int hw, int c, int ld, int coff, rn_stream_t stream);
+int rn_dense_f16_finalize(const float* partial, int n, int hw, int c, int ld, int groups, float eps, float* mean, float* rstd,
+                          rn_stream_t stream);
+int rn_dense_f16_norm(const void* buf, void* y, int n, int hw, int c, int ld, int groups, const float* mean, const float* rstd,
+                      const float* gamma, const float* beta, int act, rn_stream_t stream);
+/* What the three entry points launch for a shape: their launch decision stopped before the launch (one function).  Host only.
+ * Returns what the launch would return for valid pointers (a refused call's plan is zeroed), RN_EINVAL for a NULL plan.
+ * groups is read by finalize / norm only. */
+enum rn_dense_f16_op { RN_DENSE_F16_PUT = 1, RN_DENSE_F16_FINALIZE = 2, RN_DENSE_F16_NORM = 3 };
+typedef struct rn_dense_plan {
+  int32_t op;                  /* enum rn_dense_f16_op                                                                      */
+  int32_t vec;                 /* elements per memory access: 8 halfs (put, norm), 1 float (finalize)                        */
+  int32_t chunk;               /* pixels per statistic row                                                                   */
+  int32_t rows;                /* = rn_dense_f16_rows(hw)                                                                    */
+  int32_t octets_per_block;    /* put: channel octets a block spans (a power of two, at most 32)                             */
+  int32_t lanes;               /* put: pixel lanes of a block = threads / octets_per_block; lane l walks pixels l, l + lanes .. */
+  int32_t grid_x, grid_y, grid_z; /* put: (rows, n, octet spans); finalize: (groups, n, 1); norm: (grid-stride blocks, n, 1) */
+  int32_t threads;             /* 256                                                                                        */
+} rn_dense_plan;
+int rn_dense_f16_plan(int op, int n, int hw, int c, int ld, int coff, int groups, rn_dense_plan* plan);
+
 /* ------------------------------------------------------------------ GroupNorm (+act, +dropout, +residual)
  * Replaces normalization.py:20-35 (reshape + tf.nn.moments + affine), the activation that
  * follows it in every reference Sequential (tf.nn.elu train.py:214 / tf.nn.relu resnet.py:85),
@@ -663,6 +702,13 @@ int rn_maxpool_fwd_f16(const void* x, void* y, int n, int h, int w, int c, int k
  * per-(sample, group) mean / rstd (rn_group_norm_finalize): ResNeXt's stem (resnet.py:192-201: conv, normalization, relu,
  * max_pooling2d) without writing the normalised tensor.  Bit-equal to rn_group_norm_apply_f16 followed by rn_maxpool_fwd_f16. */
 int rn_maxpool_gn_fwd_f16(const void* x, void* y, int n, int h, int w, int c, int k, int stride, const float* mean, const float* rstd,
+                          const float* gamma, const float* beta, int groups, int act, rn_stream_t stream);
+/* fp16 inference: the 2 x 2 / 2 average pool of DenseNet's transition layer (densenet.py:124-151), TF SAME: the sum over the
+ * in-bounds cells divided by their number (rn_avgpool_fwd's rule), fp16 NHWC in and out, fp32 accumulation.  mean == NULL: the
+ * plain pool.  Otherwise y = avgpool(act(GroupNorm(x))) of the RAW x in one pass, the normalised tensor never written; every tap is
+ * rounded to fp16 as rn_group_norm_apply_f16 would store it: bit-equal to that apply pass followed by the plain pool.
+ * RN_EUNSUPPORTED: k != 2, stride != 2, c % 8 != 0, c > 2048 behind a GroupNorm.  RN_EINVAL: NULL x / y, a partly given GroupNorm. */
+int rn_avgpool_gn_fwd_f16(const void* x, void* y, int n, int h, int w, int c, int k, int stride, const float* mean, const float* rstd,
                           const float* gamma, const float* beta, int groups, int act, rn_stream_t stream);
 int rn_upsample_add_fwd_f16(const void* lateral, const void* top, void* y, int n, int h, int w, int th, int tw, int c,
                             rn_stream_t stream);

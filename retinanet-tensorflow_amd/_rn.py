@@ -22,7 +22,7 @@ LR_MAX_BOUNDARIES = 8    # RN_LR_MAX_BOUNDARIES
 LOSS_STATS_HEADER = 8
 OPT_F_NORM, OPT_F_LRDEV, OPT_F_EMA, OPT_F_CLIP, OPT_F_ACCUM, OPT_F_GATE = 1, 2, 4, 8, 16, 32    # enum rn_opt_feature
 CTL_F_ACCUM, CTL_F_GUARD, CTL_F_LR, CTL_F_EMA = 1, 2, 4, 8                                      # enum rn_ctl_feature
-API_VERSION = 426      # RN_API_VERSION of include/rn_hip.h these bindings were written against
+API_VERSION = 427     # RN_API_VERSION of include/rn_hip.h these bindings were written against
 
 
 class RnError(RuntimeError):
@@ -217,6 +217,15 @@ class DwF16Plan(C.Structure):
 DW_F16_KERNELS = {0: None, 1: "s1", 2: "s2"}       # enum rn_dw_f16_kernel
 
 
+class DenseF16Plan(C.Structure):
+    """rn_dense_f16_plan: what rn_dense_f16_put / _finalize / _norm launch for a shape (rn_dense_f16_plan, host only)"""
+    _fields_ = [(name, C.c_int32) for name in (
+        "op", "vec", "chunk", "rows", "octets_per_block", "lanes", "grid_x", "grid_y", "grid_z", "threads")]
+
+
+DENSE_F16_OPS = {"put": 1, "finalize": 2, "norm": 3}       # enum rn_dense_f16_op
+
+
 class MbRows(C.Structure):
     """rn_mb_rows"""
     _fields_ = [("rows", C.c_void_p), ("rows_per_sample", C.c_int32), ("width", C.c_int32), ("bn", C.c_int32)]
@@ -354,6 +363,7 @@ SYMBOLS = [
     "rn_step_control_eval", "rn_grad_norm_partial",
     "rn_train_metrics_workspace", "rn_train_metrics_pass", "rn_train_metrics_fold", "rn_train_metrics_reset",
     "rn_depthwise_f16_rows", "rn_depthwise_fwd_f16", "rn_depthwise_f16_plan",
+    "rn_avgpool_gn_fwd_f16", "rn_dense_f16_rows", "rn_dense_f16_put", "rn_dense_f16_finalize", "rn_dense_f16_norm", "rn_dense_f16_plan",
 ]
 
 
@@ -493,6 +503,12 @@ def lib():
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rn_maxpool_fwd_f16.argtypes = [C.c_void_p] * 2 + [C.c_int] * 6 + [C.c_void_p]
         L.rn_maxpool_gn_fwd_f16.argtypes = [C.c_void_p] * 2 + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p]
+        L.rn_avgpool_gn_fwd_f16.argtypes = [C.c_void_p] * 2 + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p]
+        L.rn_dense_f16_rows.argtypes = [C.c_int]
+        L.rn_dense_f16_put.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]
+        L.rn_dense_f16_finalize.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rn_dense_f16_norm.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        L.rn_dense_f16_plan.argtypes = [C.c_int] * 7 + [C.POINTER(DenseF16Plan)]
         L.rn_upsample_add_fwd_f16.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]
         L.rn_act_fwd_f16.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.rn_flip_width.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]

@@ -10,6 +10,8 @@ concatenated to its input (densenet.py:50-80,117-121); TransitionLayer = GN-1x1(
 with no activation (densenet.py:124-151).  k = 32; blocks 6/12/24/16 (121) or 6/12/32/32 (169).
 [GN, act] runs are one fused kernel (model.Sequential); dropout after a conv is the stand-alone
 counter-based dropout kernel.
+fp16 inference (layers.set_inference_dtype('f16')): DenseNetBC_ImageNet._call_f16 -- every dense block on one fp16 buffer
+(ops_f16.dense_block, csrc/dense_f16.hip; RN_F16_DENSE_BLOCK=0: layer by layer with a concat), transitions pool first.
 """
 import torch
 
@@ -67,13 +69,37 @@ class DenseNet_Block(Model):
         self.out_channels = c
 
     def call(self, input, training):
+        if L.INFERENCE_F16 and not training and input.is_cuda:
+            import ops_f16
+            if input.dtype == torch.float32:
+                input = ops_f16.to_half(input)
+            d = self._call_f16(input)
+            if d is not None:
+                return d.buf
         out = self._concat_free(input, training)
         if out is not None:
             return out
-        for f in self.composite_functions:               # (fp16 inference / non-bottleneck blocks: layer by layer)
+        for f in self.composite_functions:               # (fp16 concat path / non-bottleneck blocks: layer by layer)
             output = f(input, training)
             input = torch.cat([input, output], -1)       # growth concat (densenet.py:119)
         return input
+
+    def _call_f16(self, input):
+        """fp16 inference on ONE fp16 buffer (ops_f16.dense_block): per-channel sums formed once when a slice is written, every
+        layer's GroupNorm 1 from those sums, no concat.  -> the ops_f16.DenseBuffer (its .buf is the block's output), or None:
+        RN_F16_DENSE_BLOCK=0, not a bottleneck block, or a shape a kernel refuses -- the caller runs the concat path."""
+        import ops_f16
+        fns = self.composite_functions
+        if (not ops_f16.DENSE_BLOCK or not fns or not isinstance(fns[0], BottleneckCompositeFunction) or not input.is_cuda or
+                input.dtype != torch.float16):
+            return None
+        layers = []
+        for f in fns:
+            n1, a1, c1, d1, n2, a2, c2, d2 = f.layers
+            if c1.weight is None or c2.weight is None or n1.gamma is None or n2.gamma is None:
+                return None
+            layers.append((n1, c1.weight, n2, c2.weight))
+        return ops_f16.dense_block(input, layers, fns[0].layers[6].filters, L.activation_name(fns[0].layers[1]))
 
     def _concat_free(self, input, training):
         """The block on ONE pre-allocated [n,h,w,c_total] buffer (ops.dense_block): every layer normalises a channel prefix of
@@ -113,7 +139,32 @@ class TransitionLayer(Sequential):
 
     def call(self, input, training):
         assert input.shape[-1] == self.input_filters
+        if torch.is_tensor(input) and input.dtype == torch.float16 and not training:
+            out = self._call_f16(input)
+            if out is not None:
+                return out
         return super().call(input, training)
+
+    def _call_f16(self, input):
+        """fp16 inference, pool first: avgpool(conv1x1(GN(x))) = conv1x1(avgpool(GN(x))) in exact arithmetic -- the pool's weights sum
+        to 1 in every window (edge windows too), the activation-free GroupNorm is affine per (sample, channel), the 1 x 1 conv is
+        linear.  One pass reads x and writes the pooled GN(x) (ops_f16.avg_pool_norm), the conv runs on a quarter of the pixels.
+        `input`: the ops_f16.DenseBuffer of the block in front (the GroupNorm's statistics come from its table) or an fp16 tensor
+        (its sums are formed first).  None: a shape outside the kernels (the caller runs the layers in order)."""
+        import ops_f16
+        norm, conv, _, pool = self.layers
+        c = self.input_filters
+        if (conv.weight is None or norm.gamma is None or conv.bias is not None or conv.kernel_size != 1 or conv.strides != 1 or conv.groups != 1
+                or pool.pool_size != 2 or pool.strides != 2 or c % 8 or c > 2048):
+            return None
+        if isinstance(input, ops_f16.DenseBuffer):
+            d = input
+        else:
+            n, h, w, _ = input.shape
+            if not input.is_cuda or not ops_f16.dense_f16_takes('put', n, h * w, c, c):
+                return None
+            d = ops_f16.DenseBuffer.of(input)
+        return ops_f16.conv2d(ops_f16.avg_pool_norm(d.pending(norm)), conv.weight, None, 1)
 
 
 class DenseNetBC_ImageNet(Model):
@@ -141,7 +192,38 @@ class DenseNetBC_ImageNet(Model):
                 setattr(self, 'transition_layer_%d' % i, t)
                 c = t.filters
 
+    def _call_f16(self, image):
+        """The backbone in fp16 storage.  Stem: the 7 x 7 conv on the 4-channel fp16 image with the GroupNorm's statistics from its
+        epilogue, then GroupNorm + activation + max pool in one pass (ops_f16.max_pool_norm) where the conv folds; C1 (which no
+        caller of an inference pass reads) is then not materialised, as in resnet.ResNeXt.call.  Blocks on one buffer each
+        (DenseNet_Block._call_f16; the concat path where that returns None), transitions pool first with their GroupNorm's
+        statistics from the block's table.  C3 - C5 are the raw block buffers, as in fp32."""
+        import ops_f16
+        out = {'C1': None}
+        x = ops_f16.image_to_half4(image)
+        conv, norm, act = self.conv1.layers
+        pool = self.conv1_max_pool
+        p = ops_f16.conv2d_norm(x, conv.weight, norm, L.activation_name(act), conv.strides) if ops_f16.FOLD else None
+        if p is not None:
+            x = ops_f16.max_pool_norm(p, pool.pool_size, pool.strides)
+        else:
+            out['C1'] = self.conv1(x, False)
+            x = pool(out['C1'])
+        for i in range(1, 5):
+            block = getattr(self, 'dense_block_%d' % i)
+            d = block._call_f16(x)
+            x = d.buf if d is not None else block(x, False)
+            out['C%d' % (i + 1)] = x
+            if i < 4:
+                t = getattr(self, 'transition_layer_%d' % i)
+                y = t._call_f16(d) if d is not None else None
+                x = y if y is not None else t(x, False)
+        return out
+
     def call(self, input, training):
+        if (L.INFERENCE_F16 and not training and torch.is_tensor(input) and input.is_cuda and input.dtype == torch.float32
+                and input.shape[3] == 3):
+            return self._call_f16(input)
         out = {}
         input = self.conv1(input, training)
         out['C1'] = input

@@ -229,6 +229,8 @@ class AveragePooling2D(torch.nn.Module):
         self.pool_size, self.strides = pool_size, strides
 
     def forward(self, input):
+        if input.dtype == torch.float16:
+            return ops_f16.avg_pool(input, self.pool_size, self.strides)
         return ops.avg_pool(input, self.pool_size, self.strides)
 
 

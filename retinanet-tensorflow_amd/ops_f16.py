@@ -374,6 +374,133 @@ def max_pool(x, k=3, stride=2):
     return y
 
 
+def avg_pool(x, k=2, stride=2):
+    """fp16 2 x 2 / 2 average pool, TF SAME (rn_avgpool_gn_fwd_f16 without a GroupNorm)."""
+    x = x.contiguous()
+    n, h, w, c = x.shape
+    oh, _ = _rn.same_pad(h, k, stride)
+    ow, _ = _rn.same_pad(w, k, stride)
+    y = torch.empty((n, oh, ow, c), dtype=torch.float16, device=x.device)
+    _rn.check(_rn.lib().rn_avgpool_gn_fwd_f16(_rn.f16(x), _rn.f16(y), n, h, w, c, k, stride, None, None, None, None, 0, 0, _rn.stream()),
+              "rn_avgpool_gn_fwd_f16")
+    return y
+
+
+def avg_pool_norm(p, k=2, stride=2):
+    """avg_pool(act(GroupNorm(y))) of a Pending in one pass over y (rn_avgpool_gn_fwd_f16): the normalised tensor is never written.
+    Bit-equal to avg_pool(p.materialise())."""
+    y = p.y
+    n, h, w, c = y.shape
+    oh, _ = _rn.same_pad(h, k, stride)
+    ow, _ = _rn.same_pad(w, k, stride)
+    out = torch.empty((n, oh, ow, c), dtype=torch.float16, device=y.device)
+    _rn.check(_rn.lib().rn_avgpool_gn_fwd_f16(_rn.f16(y), _rn.f16(out), n, h, w, c, k, stride, _rn.f32(p.mean), _rn.f32(p.rstd),
+                                              _rn.f32(p.gamma), _rn.f32(p.beta), p.groups, _rn.ACT[p.act], _rn.stream()),
+              "rn_avgpool_gn_fwd_f16")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The DenseNet block on ONE fp16 buffer (csrc/dense_f16.hip): a DenseBuffer is the [n, h, w, ld] tensor with the table of
+# per-(sample, pixel chunk, channel) sums that every put() extends; the GroupNorm of any channel prefix takes its statistics
+# from the table (stats) -- no pass over the prefix for statistics, no torch.cat.
+# ---------------------------------------------------------------------------------------------------------------------
+DENSE_BLOCK = os.environ.get("RN_F16_DENSE_BLOCK", "1") != "0"     # (0: the block layer by layer with a concat per layer)
+
+
+def dense_f16_takes(op, n, hw, c, ld, coff=0, groups=1):
+    """True where rn_dense_f16_put / _finalize / _norm (`op`: 'put', 'finalize', 'norm') take the shape (the host-only plan)."""
+    plan = _rn.DenseF16Plan()
+    return _rn.lib().rn_dense_f16_plan(_rn.DENSE_F16_OPS[op], n, hw, c, ld, coff, groups, C.byref(plan)) == 0
+
+
+class DenseBuffer(object):
+    """buf fp16 [n, h, w, ld]; table fp32 [2, n, rows, ld]; `filled`: the channels [0, filled) are written and summed."""
+
+    def __init__(self, n, h, w, ld, device, buf=None):
+        self.n, self.h, self.w, self.ld = n, h, w, ld
+        self.buf = buf if buf is not None else torch.empty((n, h, w, ld), dtype=torch.float16, device=device)
+        self.rows = int(_rn.lib().rn_dense_f16_rows(h * w))
+        self.table = torch.empty((2, n, self.rows, ld), dtype=torch.float32, device=device)
+        self.filled = 0
+
+    @classmethod
+    def of(cls, x):
+        """The sums of a finished fp16 tensor (src == buf: the kernel reads x once and stores nothing to it)."""
+        x = x.contiguous()
+        n, h, w, c = x.shape
+        d = cls(n, h, w, c, x.device, buf=x)
+        d.put(x)
+        return d
+
+    def put(self, y):
+        """the dense fp16 [n, h, w, c] tensor y -> the next c channels of the buffer, with their sums"""
+        y = y.contiguous()
+        c = y.shape[3]
+        assert y.shape[:3] == self.buf.shape[:3] and self.filled + c <= self.ld
+        _rn.check(_rn.lib().rn_dense_f16_put(_rn.f16(y), _rn.f16(self.buf), _rn.f32(self.table), self.n, self.h * self.w, c, self.ld,
+                                             self.filled, _rn.stream()), "rn_dense_f16_put")
+        self.filled += c
+
+    def stats(self, c, groups, eps):
+        """(mean, rstd) [n, g] of the prefix [0, c), g = gn_groups(c, groups) -> (mean, rstd, g)"""
+        assert c <= self.filled
+        g = gn_groups(c, groups)
+        mean = torch.empty((self.n, g), dtype=torch.float32, device=self.buf.device)
+        rstd = torch.empty((self.n, g), dtype=torch.float32, device=self.buf.device)
+        _rn.check(_rn.lib().rn_dense_f16_finalize(_rn.f32(self.table), self.n, self.h * self.w, c, self.ld, g, float(eps), _rn.f32(mean),
+                                                  _rn.f32(rstd), _rn.stream()), "rn_dense_f16_finalize")
+        return mean, rstd, g
+
+    def norm(self, c, gamma, beta, groups, eps, act):
+        """act(GN(prefix [0, c))) as a dense fp16 [n, h, w, c] tensor (finalise, then rn_dense_f16_norm)"""
+        mean, rstd, g = self.stats(c, groups, eps)
+        a = torch.empty((self.n, self.h, self.w, c), dtype=torch.float16, device=self.buf.device)
+        _rn.check(_rn.lib().rn_dense_f16_norm(_rn.f16(self.buf), _rn.f16(a), self.n, self.h * self.w, c, self.ld, g, _rn.f32(mean), _rn.f32(rstd),
+                                              _rn.f32(gamma), _rn.f32(beta), _rn.ACT[act], _rn.stream()), "rn_dense_f16_norm")
+        return a
+
+    def pending(self, norm, act=None):
+        """the whole buffer as a Pending of the GroupNorm layer `norm` (the transition's), its statistics from the table"""
+        assert self.filled == self.ld
+        mean, rstd, g = self.stats(self.ld, norm.groups, norm.eps)
+        return Pending(self.buf, mean, rstd, norm.gamma.detach(), norm.beta.detach(), g, act)
+
+
+_dense_block_ok = {}
+
+
+def dense_block(x, layers, growth, act):
+    """A DenseNet-BC block (densenet.py:50-80,117-121) at inference on one fp16 buffer.  x: fp16 [n, h, w, c_in]; layers: per layer
+    (norm1, conv1 weight [1,1,c_i,4k], norm2, conv2 weight [3,3,4k,k]) with the layers.GroupNormalization objects; -> the
+    DenseBuffer [n, h, w, c_in + depth * growth], or None where rn_dense_f16_plan refuses a put, finalise or norm of the block (asked
+    for every slice and prefix before anything is launched; the caller takes the concat path).  A refusal of the existing conv /
+    GroupNorm kernels raises, as on the concat path.  Per layer: finalise + norm of the prefix (`a`), the 1 x 1 conv with GroupNorm 2's statistics from its epilogue
+    (conv2d_norm; conv2d + group_norm_act where the map is no whole number of m-tiles), one apply pass, the 3 x 3 conv, put."""
+    n, h, w, c_in = x.shape
+    hw, depth = h * w, len(layers)
+    ld = c_in + depth * growth
+    g0 = layers[0][0].groups
+    key = (n, hw, c_in, depth, growth, g0)
+    if key not in _dense_block_ok:       # (a function of the shape alone: asked once)
+        prefix = [c_in + i * growth for i in range(depth + 1)]      # the last one is the whole buffer: the transition's finalise
+        _dense_block_ok[key] = (dense_f16_takes('put', n, hw, c_in, ld) and all(dense_f16_takes('put', n, hw, growth, ld, c) for c in prefix[:-1])
+                                and all(dense_f16_takes('finalize', n, hw, c, ld, 0, gn_groups(c, g0)) for c in prefix)
+                                and all(dense_f16_takes('norm', n, hw, c, ld, 0, gn_groups(c, g0)) for c in prefix[:-1]))
+    if not _dense_block_ok[key]:
+        return None
+    d = DenseBuffer(n, h, w, ld, x.device)
+    d.put(x)
+    for i, (norm1, w1, norm2, w2) in enumerate(layers):
+        c = c_in + i * growth
+        a = d.norm(c, norm1.gamma.detach(), norm1.beta.detach(), norm1.groups, norm1.eps, act)
+        p = conv2d_norm(a, w1, norm2, act) if FOLD else None
+        y1 = p.materialise() if p is not None else group_norm_act(conv2d(a, w1), norm2.gamma.detach(), norm2.beta.detach(), norm2.groups,
+                                                                  norm2.eps, act)
+        d.put(conv2d(y1, w2))
+    return d
+
+
 def upsample_add(lateral, top):
     lateral, top = lateral.contiguous(), top.contiguous()
     n, h, w, c = lateral.shape

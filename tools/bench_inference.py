@@ -2,7 +2,8 @@
 anchor decode + batched class-wise NMS, in fp32 and in fp16 storage (f16 matrix-core convs, fp32 accumulate).
     python tools/bench_inference.py [backbone [size [batch [iters [rounds]]]]]
 With mobilenet_v2 the fp16 pass runs for both values of RN_F16_MB_BACKBONE (mobilenet_v2.F16_BACKBONE: 1 the backbone in fp16,
-0 the backbone in fp32 with its taps cast); `rounds` repeats the whole set interleaved (f32, f16 ..., f32, f16 ...) in one process."""
+0 the backbone in fp32 with its taps cast), with densenet_121 / densenet_169 for both values of RN_F16_DENSE_BLOCK (ops_f16.DENSE_BLOCK:
+1 the dense blocks on one fp16 buffer each, 0 layer by layer with a concat per layer); `rounds` repeats the whole set interleaved (f32, f16 ..., f32, f16 ...) in one process."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "retinanet-tensorflow_amd")):
@@ -32,9 +33,17 @@ def main(backbone="resnet_50", size=1024, batch=16, iters=5, rounds=1):
     if backbone == "mobilenet_v2":
         import mobilenet_v2
         passes = [("f32", None), ("f16", 1), ("f16", 0)]
+    dense = backbone.startswith("densenet")
+    if dense:
+        import ops_f16
+        passes = [("f32", None), ("f16", 1), ("f16", 0)]
     for rnd, (dtype, mb_switch) in [(r, p) for r in range(rounds) for p in passes]:
         layers.set_inference_dtype(dtype)
-        if mb_switch is not None:
+        if dense:
+            dense_switch, mb_switch = mb_switch, None
+            if dense_switch is not None:
+                ops_f16.DENSE_BLOCK = bool(dense_switch)
+        elif mb_switch is not None:
             mobilenet_v2.F16_BACKBONE = bool(mb_switch)
         o = run(); torch.cuda.synchronize()
         counts = o[5].cpu().tolist()
@@ -61,7 +70,7 @@ def main(backbone="resnet_50", size=1024, batch=16, iters=5, rounds=1):
             except Exception as e:       # (reported, not fatal: the eager figure stands)
                 graph_ips = "failed: %s" % (str(e)[:120],)
         print(json.dumps({"backbone": backbone, "image_size": size, "batch": batch, "dtype": dtype, "round": rnd,
-                          "RN_F16_MB_BACKBONE": mb_switch,
+                          "RN_F16_MB_BACKBONE": mb_switch, "RN_F16_DENSE_BLOCK": dense_switch if dense else None,
                           "images_per_sec": round(batch / el, 2), "ms_per_batch": round(el * 1e3, 2),
                           "images_per_sec_graph": graph_ips,
                           "candidates": counts[0], "kept": counts[1], "conv_TFLOPs": round(596.0 * batch / el / 1e3, 1) if (backbone, size) == ("resnet_50", 1024) else None,
